@@ -14,7 +14,13 @@ default): sample chunks of up to 2^28 paths with 40% of HBM per chunk
 pipeline (ptg_set_chunk_paths / ptg_set_hbm_share); --gpu-memory shared keeps
 the library's defaults for a shared GPU; the bits are the same.
 
-Beside `value` the line carries (rank 0):
+A plain run does only what `value` needs: it sets up, warms up, times --steps
+render steps, writes the last step's outputs when --dump-outputs is given and
+prints the line.  Everything below takes runs of its own and is measured only
+with --full (the options that trim it, --no-roofline, --animation K, ..., act
+under --full).
+
+Beside `value` the line carries under --full (rank 0):
   with_frame_setup  what main.cc does per frame - setup_animation_frame (host
                     C++) + H2D upload + render, pipelined (PCIe-inclusive,
                     never `value`);
@@ -38,7 +44,7 @@ Multi-GPU: one process per GPU (torch.distributed.run).  `--gpus N` with N >
 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 torch.distributed.run, before anything touches a GPU) and forwards its
 output and exit code; a WORLD_SIZE that is not --gpus exits with status 2.
-At N > 1 the line also carries `strong`: the metric frame in interleaved
+At N > 1 the --full line also carries `strong`: the metric frame in interleaved
 tiles over the same ranks, gathered on rank 0 by one RCCL gather.  --shard frames
 (default): rank r renders frame (frame + r) - weak scaling, no collective on
 the data path (BASELINE config 4 style).  --shard tiles: one frame split into
@@ -392,6 +398,14 @@ def main():
                     help="owned (default: the bench process owns its GPU): 2^28-path sample chunks, <= 40%% of HBM "
                          "per chunk pipeline (ptg_set_chunk_paths / ptg_set_hbm_share); shared: the library's "
                          "defaults (2^27, 35%%), which leave most of the GPU to other tenants.  Same bits either way")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the self-test, the frame "
+                         "against the reference's hashes, the upload and frame-setup loops, the heavy frame, the "
+                         "animation, the rooflines and the CPU baseline (the options below trim these legs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the "
+                         "BGRA framebuffer and, unless --shard tiles, the accumulated radiance; at most 64 MB in "
+                         "all (a fixed, seeded sample of the pixels beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--config", type=int, default=None, choices=[1, 2, 3, 4],
@@ -434,6 +448,9 @@ def main():
         args.width, args.height, args.spp, args.frame, args.shard = 3840, 2160, 4096, 690, "tiles"
         args.heavy_frame = -1
     is_metric = (args.width, args.height, args.spp) == (1280, 720, 1024)
+    if not args.full:   # a plain run: the timed steps and nothing beside them
+        args.no_cpu_baseline = args.no_roofline = args.no_frame_setup = True
+        args.heavy_frame, args.animation = -1, 0
     if args.animation is None:
         args.animation = 30 if is_metric else 0
 
@@ -480,7 +497,7 @@ def main():
     r = GpuRenderer(local)
     # the arithmetic environment the bit-exact results rest on (ptg_arith_selftest)
     try:
-        selftest = r.selftest()
+        selftest = r.selftest() if args.full else None
     except RuntimeError as e:   # a timing variant without the self-test (tools/variants/at_commit.py): never "passed"
         selftest = "unavailable: %s" % e
     stream = torch.cuda.current_stream(local)
@@ -732,13 +749,27 @@ def main():
                            "shades": round(total[5] / per_step_samples, 3)}})
         return roof
 
+    def dump_outputs(directory, tensors, budget=64 << 20):
+        """<name>.npy (float32) of each tensor [H][W][C], whole while all of them
+        fit `budget` bytes, else the same seeded sample of the pixels of each."""
+        os.makedirs(directory, exist_ok=True)
+        pixels = cfg.width * cfg.height
+        keep = budget // sum(4 * t.shape[-1] for t in tensors.values())
+        pick = None if keep >= pixels else np.sort(np.random.default_rng(0).choice(pixels, keep, replace=False))
+        for name, t in tensors.items():
+            a = t.cpu().numpy().astype(np.float32).reshape(pixels, -1)
+            np.save(os.path.join(directory, name + ".npy"), a.reshape(t.shape) if pick is None else a[pick])
+
     def workload_of(f):
         return "frame %d, %dx%d, %d spp, %d bounces" % (f, cfg.width, cfg.height, cfg.samples_per_pixel,
                                                          cfg.max_bounces)
 
     # (1) the metric: render steps over a frame whose inputs are resident in HBM
+    # (per-kernel HIP events on in plain runs too: the steps are timed under the same conditions either way)
     elapsed, kb = timed(render_step, True, tag="metric")
-    main_check = frame_check(frame)   # this rank's last timed image against the reference's
+    if args.dump_outputs and rank == 0:   # before any other leg overwrites the buffers
+        dump_outputs(args.dump_outputs, {"image": image} if shard is not None else {"image": image, "accum": accum})
+    main_check = frame_check(frame) if args.full else None   # this rank's last timed image against the reference's
     # (2) SURVEY 8(d)'s definition: W.H.SPP / (upload-frame + render + gather)
     elapsed_upload = None if args.no_frame_setup else timed(upload_step, False)[0]
     # (3) the reference's per-frame loop: host setup_animation_frame + PCIe upload + render
@@ -753,7 +784,7 @@ def main():
     # the metric frame itself cut into interleaved tiles over the same ranks
     # and assembled on rank 0 by one RCCL gather (BASELINE configs[2])
     strong = None
-    if world > 1 and args.shard == "frames":
+    if args.full and world > 1 and args.shard == "frames":
         scene.setup_frame(args.frame)
         r.upload(scene, include_static=False)
         tshard = D.TileShard(cfg, tw, th, rank, world)
@@ -907,7 +938,7 @@ def main():
             "frame_exact": None if main_check is None else main_check["exact"],
             "frame_check": main_check,
             "selftest": selftest,
-            "libm": libm_identity(),
+            "libm": libm_identity() if args.full else None,
             "ranks": ranks,
             "per_rank_seconds": {k: [round(x, 4) for x in v] for k, v in per_rank_s.items()} if world > 1 else None,
             "strong": strong,

@@ -7,7 +7,9 @@ so ``load_scene`` would exit at ``mesh.cc:25-29``.  This module assembles a
 self-contained asset directory ``<dest>/data`` that both the reference build
 (the test oracle's checker) and this framework load:
 
-* every OBJ/MTL the reference ships is copied byte-for-byte;
+* every OBJ/MTL the reference ships is restored byte-for-byte from the
+  committed fixtures ``tests/golden/scene`` (``.mtl`` as they are, ``.obj``
+  xz-compressed: every committed file stays below 1 MiB);
 * the three missing meshes are replaced by deterministic substitutes
   (SURVEY.md §8c recipe):
     - ``terrain.obj``: 129x129 heightfield over x,z in [-110, 110],
@@ -21,17 +23,18 @@ self-contained asset directory ``<dest>/data`` that both the reference build
       ``Material.010`` / ``Material.011``.
 
 The generator is pure Python with fixed ``%.6f`` formatting, so the bytes are
-identical on every machine.  The GPU box receives the prepared directory with
-the repository snapshot (it is git-ignored, not gpurun-ignored).
+identical on every machine.  The prepared directory is git-ignored: a fresh
+checkout rebuilds it from the committed fixtures alone.
 """
 from __future__ import annotations
 
 import hashlib
+import lzma
 import math
 import os
 import shutil
 
-REFERENCE_DATA = "/root/reference/data"
+FIXTURES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "scene")
 MISSING = ("terrain.obj", "bunny.obj", "pine_tree.obj")
 
 TERRAIN_N = 129
@@ -93,7 +96,12 @@ def _renamed(src_text: str, renames: dict) -> str:
     return "\n".join(lines)
 
 
-def prepare(dest: str, reference_data: str = REFERENCE_DATA, force: bool = False) -> str:
+def _fixture_text(fixtures: str, name: str) -> str:
+    with lzma.open(os.path.join(fixtures, name + ".xz"), "rt") as f:
+        return f.read()
+
+
+def prepare(dest: str, fixtures: str = FIXTURES, force: bool = False) -> str:
     """Create ``<dest>/data`` with the full scene.  Returns ``dest``.
 
     If the directory is already complete (a ``MANIFEST`` file is present) and
@@ -103,22 +111,23 @@ def prepare(dest: str, reference_data: str = REFERENCE_DATA, force: bool = False
     manifest = os.path.join(dest, "MANIFEST")
     if os.path.exists(manifest) and not force:
         return dest
-    if not os.path.isdir(reference_data):
+    if not os.path.isdir(fixtures):
         raise FileNotFoundError(
-            "scene assets missing: %s has no MANIFEST and the reference data "
-            "directory %s is not available to rebuild it" % (dest, reference_data))
+            "scene assets missing: %s has no MANIFEST and the fixture "
+            "directory %s is not available to rebuild it" % (dest, fixtures))
     os.makedirs(data, exist_ok=True)
-    for name in sorted(os.listdir(reference_data)):
-        if name.endswith((".obj", ".mtl")):
-            shutil.copyfile(os.path.join(reference_data, name), os.path.join(data, name))
+    for name in sorted(os.listdir(fixtures)):
+        if name.endswith(".mtl"):
+            shutil.copyfile(os.path.join(fixtures, name), os.path.join(data, name))
+        elif name.endswith(".obj.xz"):
+            with lzma.open(os.path.join(fixtures, name), "rb") as src, open(os.path.join(data, name[:-3]), "wb") as f:
+                shutil.copyfileobj(src, f)
     with open(os.path.join(data, "terrain.obj"), "w", newline="\n") as f:
         f.write(_terrain_obj())
-    with open(os.path.join(reference_data, "teapot.obj")) as f:
-        teapot = f.read()
+    teapot = _fixture_text(fixtures, "teapot.obj")
     with open(os.path.join(data, "bunny.obj"), "w", newline="\n") as f:
         f.write(_renamed(teapot, {"teapot.mtl": "bunny.mtl", "Material.005": "Material.024"}))
-    with open(os.path.join(reference_data, "leaf_tree.obj")) as f:
-        leaf = f.read()
+    leaf = _fixture_text(fixtures, "leaf_tree.obj")
     with open(os.path.join(data, "pine_tree.obj"), "w", newline="\n") as f:
         f.write(_renamed(leaf, {"leaf_tree.mtl": "pine_tree.mtl", "Material.006": "Material.010",
                                 "Material.007": "Material.011"}))

@@ -11,6 +11,7 @@ mkdir -p gpurun_out
 timeout -k 10 1000 bash tools/profile_gpu.sh $TAG > gpurun_out/profile_$TAG.txt 2>&1 || { tail -20 gpurun_out/profile_$TAG.txt; exit 1; }
 python3 tools/summarize_prof.py gpurun_out/prof_$TAG $TAG > gpurun_out/summarize_$TAG.txt 2>&1 || { tail -20 gpurun_out/summarize_$TAG.txt; exit 1; }
 mkdir -p gpurun_out/profiles_$TAG && cp -r profiles/$TAG/. gpurun_out/profiles_$TAG/
-timeout -k 10 1100 python bench.py > gpurun_out/bench.txt 2>&1 || { tail -20 gpurun_out/bench.txt; exit 1; }
-grep '^{' gpurun_out/bench.txt | tail -1 > gpurun_out/profiles_$TAG/bench_line.json
+BENCH_TXT=$(mktemp)
+timeout -k 10 1100 python bench.py --full > $BENCH_TXT 2>&1 || { tail -20 $BENCH_TXT; exit 1; }
+grep '^{' $BENCH_TXT | tail -1 > profiles/$TAG/bench_line.json
 echo done

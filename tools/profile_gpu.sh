@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-frame-setup --animation 0 --heavy-frame -1 --concurrency 0 $*"
+BENCH="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-frame-setup --animation 0 --heavy-frame -1 --concurrency 0 $*"
 cd /tmp
 if [ -z "$NO_TRACE" ]; then
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $BENCH > $OUT/trace.log 2>&1 || { echo "trace pass failed"; tail -20 $OUT/trace.log; exit 1; }

@@ -12,7 +12,7 @@ for mode in frames tiles samples; do
   port=$((port + 1))
   PTG_BENCH_REHEARSE=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port $port bench.py --gpus 2 --steps 2 --warmup 1 --width 640 --height 360 \
-    --spp 64 --heavy-frame -1 --animation 2 --no-cpu-baseline --no-frame-setup --no-roofline --shard $mode \
+    --spp 64 --full --heavy-frame -1 --animation 2 --no-cpu-baseline --no-frame-setup --no-roofline --shard $mode \
     > gpurun_out/rehearse_$mode.txt 2>&1 || { echo "rehearse $mode failed"; tail -20 gpurun_out/rehearse_$mode.txt; exit 1; }
   grep '^{' gpurun_out/rehearse_$mode.txt | python3 -c "
 import json, sys
@@ -23,7 +23,7 @@ done
 # bench.py launching its own ranks (no external launcher):
 # the weak (frames) value plus the strong tile sub-record in one line
 PTG_BENCH_REHEARSE=1 timeout -k 10 400 python3 bench.py --gpus 2 --steps 2 --warmup 1 --width 640 --height 360 \
-  --spp 64 --heavy-frame -1 --animation 2 --no-cpu-baseline --no-frame-setup --no-roofline \
+  --spp 64 --full --heavy-frame -1 --animation 2 --no-cpu-baseline --no-frame-setup --no-roofline \
   > gpurun_out/rehearse_self.txt 2>&1 || { echo "rehearse self-launch failed"; tail -20 gpurun_out/rehearse_self.txt; exit 1; }
 grep '^{' gpurun_out/rehearse_self.txt | python3 -c "
 import json, sys
