@@ -247,6 +247,64 @@ int ptg_tonemap_device(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_
  * is accepted. */
 int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* rays, uint32_t* hits);
 
+/* The first ray path_trace_pixel traces for each (pixel, sample_index) pair:
+ * the seed, the film jitter and get_camera_ray (path_tracer.hh:659-671,
+ * :429-450).  rays gets 8 floats per pair, the layout ptg_trace_rays takes:
+ * {origin.xyz, dir.xyz, 0, MAX_RAY_DIST (1e9)}; subframe gets
+ * sample_index / samples_per_motion_blur_step, the subframe whose camera and
+ * TLAS the sample uses.  HOST pointers; synchronous. */
+int ptg_camera_rays(ptg_context* ctx, const ptg_render_config* cfg, size_t n,
+                    const ptg_uint2* xy, const int32_t* sample_index,
+                    float* rays /* n x 8 */, uint32_t* subframe /* n */);
+
+/* ---- first-hit feature buffers and the denoiser -------------------------
+ * What the first ray of every sample saw, averaged like the radiance.  With
+ * the rectangle and sample-range meaning of ptg_render: each sample j of
+ * [sample_begin, sample_end) casts the camera ray of (pixel, j)
+ * (ptg_camera_rays) and takes its closest hit in that sample's subframe.
+ *   hit:  albedo = the interpolated vertex albedo (path_tracer.hh:373-392),
+ *         coverage 1, normal = the unit world-space shading normal, flipped on
+ *         a back face (the vector trace_ray builds its tangent space from),
+ *         depth = the hit distance
+ *   miss: albedo (1,1,1), coverage 0, normal (0,0,0), depth 0
+ * out_albedo = (sum albedo.rgb, sum coverage), out_normal_depth =
+ * (sum normal.xyz, sum depth): each component summed in float32 in sample
+ * order starting from +0, then divided by cfg->samples_per_pixel.
+ * DEVICE pointers, [h][w] ptg_float4 each; asynchronous on the context's
+ * stream. */
+int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg,
+                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                        uint32_t sample_begin, uint32_t sample_end,
+                        ptg_float4* out_albedo, ptg_float4* out_normal_depth);
+
+/* Edge-avoiding a-trous wavelet denoiser over the radiance, guided by the two
+ * feature buffers.  Every operation is one float32 rounding in a fixed order
+ * and the weights' exp is glibc's double exp, so a CPU restatement reproduces
+ * the output bit for bit (DESIGN.md has the definition; the package's
+ * denoise.atrous_reference is that restatement).  A pixel with a non-finite
+ * channel is never used as a tap and is itself replaced by the weighted mean
+ * of its finite neighbours. */
+typedef struct {
+    uint32_t iterations;   /* 0..8 passes; pass k has taps 2^k pixels apart */
+    float sigma_color;     /* demodulated-radiance distance scale (halved every pass) */
+    float sigma_albedo;    /* albedo + coverage distance scale */
+    float sigma_normal;    /* normal distance scale */
+    float sigma_depth;     /* relative depth distance scale */
+    float albedo_floor;    /* radiance is divided by max(albedo, albedo_floor) before filtering */
+} ptg_denoise_params;
+void ptg_denoise_params_default(ptg_denoise_params* params);
+/* radiance, albedo, normal_depth: [h][w] ptg_float4 as written by ptg_render
+ * (out_accum) and ptg_render_features.  out_radiance ([h][w], w component 0)
+ * may be the same buffer as radiance; out_bgra (optional) is tonemap_pixel of
+ * it.  The intermediate images belong to the context.  iterations > 8, or a
+ * sigma or albedo_floor that is not positive and finite, is PTG_E_INVALID;
+ * iterations == 0 copies the radiance bits unchanged.  DEVICE pointers;
+ * asynchronous on the context's stream. */
+int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_params* params,
+                const ptg_float4* radiance, const ptg_float4* albedo,
+                const ptg_float4* normal_depth,
+                ptg_float4* out_radiance, ptg_uchar4* out_bgra);
+
 /* Work counters of the last ptg_render* call (filled only while counting is
  * on, ptg_counters_enable; counting uses a separate, slower build of the
  * kernels):

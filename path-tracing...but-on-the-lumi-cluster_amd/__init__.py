@@ -8,6 +8,8 @@ Python identifier).  Layout:
                    host C++ scene restatement (csrc/host/) -> _build/libptg.so
   native.py        ctypes binding of include/ptg.h
   renderer.py      GpuRenderer: upload + render through the C ABI
+  denoise.py       DenoiseParams and atrous_reference, the CPU restatement of
+                   ptg_denoise (NumPy float32 + the C library's exp)
   distributed.py   one process per GPU: tile / frame sharding, RCCL gather
   validator.py     validator.py-equivalent PSNR check (numpy)
   assets.py        scene asset preparation (reference OBJs + substitutes)

@@ -20,6 +20,7 @@
 #include "device/wavefront.h"
 #include "ptg_device.h"   // ptg_device_selftest, compiled here with the library's own flags (ptg_arith_selftest)
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -784,6 +785,194 @@ __global__ void k_scatter_tiles(PixelMap pm, const uchar4* __restrict__ tiles, u
     if(pm.pixel(p, x, y)) image[size_t(y) * pm.img_w + x] = tiles[p];
 }
 
+// ---- first-hit feature buffers and the a-trous denoiser ----
+
+// The first ray path_trace_pixel traces for (pixel, sample): camera_ray's
+// origin and direction with tmin 0 and tmax MAX_RAY_DIST, and the subframe.
+__global__ __launch_bounds__(kBlock) void k_camera_rays(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
+                                                        const int32_t* __restrict__ js, float* __restrict__ rays,
+                                                        uint32_t* __restrict__ subframe)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) return;
+    const uint8_t* sf = subframe_of(sc, js[i]);
+    u4 seed;
+    f3 o, d;
+    camera_ray(sc, sf, xy[i].x, xy[i].y, js[i], seed, o, d);
+    float* r = rays + size_t(i) * 8;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z;
+    r[3] = d.x; r[4] = d.y; r[5] = d.z;
+    r[6] = 0.0f; r[7] = MAX_RAY_DIST;
+    subframe[i] = (uint32_t)(sf - sc.subframes) / SF_STRIDE;
+}
+
+// Feature pass.  A wave holds 8 pixels x 8 consecutive samples, as k_trace
+// does (lanes 0-7 are samples jb..jb+7 of the wave's pixel 0, and so on), so
+// its primary rays are neighbours in the image and in time; it walks the
+// sample range in groups of 8.  After each group the 8 lanes of a pixel fold
+// the group's 8 values into the pixel's sums in sample order (every lane of
+// the pixel keeps the same sums), so each component is the float32 sum
+// ((0 + s_j0) + s_j0+1) + ... whatever the lane mapping.
+__global__ __launch_bounds__(kBlock) void k_features(DevScene sc, PixelMap pm, uint32_t j0, uint32_t j1, float spp,
+                                                     float4* __restrict__ out_albedo,
+                                                     float4* __restrict__ out_normal_depth)
+{
+    // the walk stacks: the wavefront walks' LDS windows (LdsStack), one 64-lane
+    // x kCap table per wave, with the lane's spill area in sc.spill
+    __shared__ uint2 windows[kBlock * LdsStack::kCap];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t k = lane & 7u;
+    BlockWalker<RegCold, LdsStack> w;
+    w.st.bind(windows, threadIdx.x >> 6, lane, sc.spill + (size_t(blockIdx.x) * blockDim.x + threadIdx.x) * sc.spill_stride);
+    // persistent blocks: block b takes the 32-pixel groups b, b + gridDim.x, ...
+    const uint32_t groups = (pm.npix + kBlock / 8u - 1u) / (kBlock / 8u);
+    for(uint32_t pb = blockIdx.x; pb < groups; pb += gridDim.x)
+    {
+        const uint32_t p = pb * (kBlock / 8u) + (threadIdx.x >> 3);
+        uint32_t x = 0, y = 0;
+        const bool inside = p < pm.npix && pm.pixel(p, x, y);
+        float acc[8];
+#pragma unroll
+        for(int c = 0; c < 8; ++c) acc[c] = 0.0f;
+        for(uint32_t jb = j0; jb < j1; jb += 8u)
+        {
+            // miss: albedo (1,1,1), coverage 0, normal 0, depth 0
+            float v[8] = {1.0f, 1.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            const uint32_t j = jb + k;
+            bool active = inside && j < j1;
+            const uint8_t* sf = subframe_of(sc, (int32_t)(active ? j : j0));
+            f3 o = V3(0, 0, 0), d = V3(0, 0, 1);
+            Counters cnt;
+            if(active)
+            {
+                uint32_t tc, to;
+                tlas_of(sc, sf, tc, to);
+                u4 seed;
+                camera_ray(sc, sf, x, y, (int32_t)j, seed, o, d);
+                w.init(tc, o, d, 0.0f, MAX_RAY_DIST);
+            }
+            // the wave walks in phases as k_wf_walk does: node steps for the lanes
+            // not standing at a leaf, then one leaf phase for the lanes that are
+            const bool traced = active;
+            while(__any(active))
+            {
+#pragma unroll
+                for(int u = 0; u < kWalkUnroll; ++u)
+                    if(active && !w.at_leaf() && w.template node_step<false>(sc, cnt) != 0) active = false;
+                if(active && w.wants_leaf() && w.template leaf_step<false, false>(sc, cnt) != 0) active = false;
+            }
+            if(traced)
+            {
+                const Hit h = w.result();
+                if(!(h.thit < 0))
+                {
+                    const HitInfo hi = hit_info<false, 0>(sc, light_of(sf), o, d, h, cnt);
+                    const f3 n = hi.tbn.r[2];   // tangent_space keeps its argument as the third row
+                    v[0] = hi.albedo.x; v[1] = hi.albedo.y; v[2] = hi.albedo.z; v[3] = 1.0f;
+                    v[4] = n.x; v[5] = n.y; v[6] = n.z; v[7] = hi.thit;
+                }
+            }
+            const uint32_t group = j1 - jb < 8u ? j1 - jb : 8u;
+            for(uint32_t s = 0; s < group; ++s)
+            {
+                const int src = (int)((lane & 56u) + s);
+#pragma unroll
+                for(int c = 0; c < 8; ++c) acc[c] = acc[c] + __shfl(v[c], src);
+            }
+        }
+        if(inside && k == 0)
+        {
+            out_albedo[p] = make_float4(acc[0] / spp, acc[1] / spp, acc[2] / spp, acc[3] / spp);
+            out_normal_depth[p] = make_float4(acc[4] / spp, acc[5] / spp, acc[6] / spp, acc[7] / spp);
+        }
+    }
+}
+
+// max(albedo, floor) of the denoiser's (de)modulation; a NaN albedo stays NaN
+__device__ __forceinline__ float dn_floor(float a, float fl) { return (a > fl || a != a) ? a : fl; }
+
+// I0 = radiance / max(albedo, floor) per channel
+__global__ __launch_bounds__(kBlock) void k_dn_demodulate(uint32_t n, float fl, const float4* __restrict__ radiance,
+                                                          const float4* __restrict__ albedo, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) return;
+    const float4 r = radiance[i], a = albedo[i];
+    out[i] = make_float4(r.x / dn_floor(a.x, fl), r.y / dn_floor(a.y, fl), r.z / dn_floor(a.z, fl), 0.0f);
+}
+
+struct DenoiseStep {
+    uint32_t w, h, step;
+    float var_color, var_albedo, var_normal, var_depth;   // sigma * sigma of this iteration
+};
+
+// One edge-avoiding a-trous iteration, one work-item per pixel: 5 x 5 taps
+// `step` pixels apart, dy outer and dx inner, every operation one float32
+// rounding in the order DESIGN.md gives; the weight's exp is glibc's.
+__global__ __launch_bounds__(kBlock) void k_dn_atrous(DenoiseStep a, const float4* __restrict__ I,
+                                                      const float4* __restrict__ albedo,
+                                                      const float4* __restrict__ normal_depth, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= a.w * a.h) return;
+    const int32_t x = (int32_t)(i % a.w), y = (int32_t)(i / a.w);
+    const float4 Ip = I[i], Ap = albedo[i], Np = normal_depth[i];
+    const bool p_finite = finite3(V3(Ip.x, Ip.y, Ip.z));
+    const float zp2 = Np.w * Np.w;
+    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    for(int32_t dy = -2; dy <= 2; ++dy)
+    {
+        const int64_t qy = (int64_t)y + (int64_t)dy * a.step;
+        if(qy < 0 || qy >= (int64_t)a.h) continue;
+        const float hy = dy == 0 ? 0.375f : (dy == -1 || dy == 1) ? 0.25f : 0.0625f;
+        for(int32_t dx = -2; dx <= 2; ++dx)
+        {
+            const int64_t qx = (int64_t)x + (int64_t)dx * a.step;
+            if(qx < 0 || qx >= (int64_t)a.w) continue;
+            const float hx = dx == 0 ? 0.375f : (dx == -1 || dx == 1) ? 0.25f : 0.0625f;
+            const size_t q = size_t(qy) * a.w + size_t(qx);
+            const float4 Iq = I[q];
+            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
+            const float4 Aq = albedo[q], Nq = normal_depth[q];
+            float dc = 0.0f;
+            if(p_finite)
+            {
+                const float cx = Ip.x - Iq.x, cy = Ip.y - Iq.y, cz = Ip.z - Iq.z;
+                dc = (cx * cx + cy * cy) + cz * cz;
+            }
+            const float ax = Ap.x - Aq.x, ay = Ap.y - Aq.y, az = Ap.z - Aq.z, aw = Ap.w - Aq.w;
+            const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
+            const float nx = Np.x - Nq.x, ny = Np.y - Nq.y, nz = Np.z - Nq.z;
+            const float dn = (nx * nx + ny * ny) + nz * nz;
+            const float dz = Np.w - Nq.w;
+            const float zq2 = Nq.w * Nq.w;
+            const float zmax = (zp2 > zq2 || zp2 != zp2) ? zp2 : zq2;   // a NaN depth stays NaN
+            const float dz2 = (dz * dz) / (zmax + 1e-12f);
+            const float e = ((dc / a.var_color + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
+            if(!__builtin_isfinite(e)) continue;
+            const float wgt = (hy * hx) * (float)dexp(-(double)e);
+            sw = sw + wgt;
+            sx = sx + wgt * Iq.x;
+            sy = sy + wgt * Iq.y;
+            sz = sz + wgt * Iq.z;
+        }
+    }
+    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, 0.0f) : make_float4(Ip.x, Ip.y, Ip.z, 0.0f);
+}
+
+// out = I * max(albedo, floor), w = 0; optionally its tonemap
+__global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, const float4* __restrict__ I,
+                                                          const float4* __restrict__ albedo, float4* __restrict__ out,
+                                                          uchar4* __restrict__ out_bgra)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) return;
+    const float4 v = I[i], a = albedo[i];
+    const f3 c = V3(v.x * dn_floor(a.x, fl), v.y * dn_floor(a.y, fl), v.z * dn_floor(a.z, fl));
+    out[i] = make_float4(c.x, c.y, c.z, 0.0f);
+    if(out_bgra) out_bgra[i] = tonemap(c);
+}
+
 // ---------------------------------------------------------------- runtime --
 
 struct DevBuf {
@@ -887,6 +1076,8 @@ struct ptg_context {
     bool frame_ready = false;
     // render workspace
     DevBuf samples, acc, tmp_a, tmp_b, tmp_c, counters;
+    DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
+    DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
     DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
     uint64_t last_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // k_trace launch timing (HIP events on the launch stream)
@@ -2007,6 +2198,128 @@ int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* r
     PTG_HIP(hipGetLastError());
     PTG_HIP(hipMemcpyAsync(hits, ctx->tmp_b.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
+    return PTG_OK;
+}
+
+int ptg_camera_rays(ptg_context* ctx, const ptg_render_config* cfg, size_t n, const ptg_uint2* xy,
+                    const int32_t* sample_index, float* rays, uint32_t* subframe)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, 0)) return r;
+    if(!n) return PTG_OK;
+    if(!xy || !sample_index || !rays || !subframe || n >= (1u << 28)) return fail(PTG_E_INVALID, "ptg_camera_rays: bad arguments");
+    int32_t jmax = 0;
+    for(size_t i = 0; i < n; ++i)
+    {
+        jmax = std::max(jmax, sample_index[i]);
+        if(xy[i].x >= cfg->width || xy[i].y >= cfg->height) return fail(PTG_E_RANGE, "pixel outside the image");
+    }
+    if(uint64_t(jmax) / cfg->samples_per_motion_blur_step >= ctx->subframe_count)
+        return fail(PTG_E_RANGE, "sample index beyond the frame's subframes");
+    PTG_HIP(ctx->grow(ctx->tmp_a, n * sizeof(uint2)));
+    PTG_HIP(ctx->grow(ctx->tmp_b, n * sizeof(int32_t)));
+    PTG_HIP(ctx->grow(ctx->tmp_c, n * 36));            // n rays of 8 floats, then n subframe indices
+    float* d_rays = ctx->tmp_c.as<float>();
+    uint32_t* d_sub = reinterpret_cast<uint32_t*>(d_rays + n * 8);
+    PTG_HIP(hipMemcpyAsync(ctx->tmp_a.p, xy, n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    PTG_HIP(hipMemcpyAsync(ctx->tmp_b.p, sample_index, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(cfg), uint32_t(n),
+                       ctx->tmp_a.as<uint2>(), ctx->tmp_b.as<int32_t>(), d_rays, d_sub);
+    PTG_HIP(hipGetLastError());
+    PTG_HIP(hipMemcpyAsync(rays, d_rays, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    PTG_HIP(hipMemcpyAsync(subframe, d_sub, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PTG_HIP(hipStreamSynchronize(ctx->stream));
+    return PTG_OK;
+}
+
+int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                        uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, sample_end)) return r;
+    if(uint64_t(x0) + w > cfg->width || uint64_t(y0) + h > cfg->height) return fail(PTG_E_RANGE, "rectangle outside the image");
+    if(uint64_t(w) * h == 0) return PTG_OK;
+    if(!out_albedo || !out_normal_depth) return fail(PTG_E_INVALID, "ptg_render_features: null output");
+    if(sample_end <= sample_begin) return fail(PTG_E_INVALID, "empty sample range");
+    PixelMap pm{};
+    pm.tiles = 0;
+    pm.x0 = x0; pm.y0 = y0; pm.w = w; pm.h = h;
+    pm.img_w = cfg->width; pm.img_h = cfg->height;
+    pm.npix = w * h;
+    // persistent blocks, each taking groups of kBlock / 8 pixels (4 waves of 8
+    // pixels x 8 samples); every walk lane owns stack_bound entries of spill
+    const uint32_t grid = std::min<uint32_t>(grid_for(pm.npix, kBlock / 8), std::max(1u, ctx->persistent_blocks / 4u));   // 8 per CU
+    PTG_HIP(ctx->grow(ctx->feat_spill, std::max<size_t>(1, size_t(grid) * kBlock * ctx->stack_bound) * sizeof(uint2)));
+    DevScene sc = ctx->scene_args(cfg);
+    sc.spill = ctx->feat_spill.as<uint2>();
+    hipLaunchKernelGGL(k_features, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, pm,
+                       sample_begin, sample_end, (float)cfg->samples_per_pixel, reinterpret_cast<float4*>(out_albedo),
+                       reinterpret_cast<float4*>(out_normal_depth));
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+void ptg_denoise_params_default(ptg_denoise_params* p)
+{
+    if(!p) return;
+    // the best row of tools/denoise_study.py's sweep (profiles/denoise_study/)
+    p->iterations = 4;
+    p->sigma_color = 2.0f;
+    p->sigma_albedo = 0.05f;
+    p->sigma_normal = 1.2f;
+    p->sigma_depth = 1.0f;
+    p->albedo_floor = 0.01f;
+}
+
+int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_params* params, const ptg_float4* radiance,
+                const ptg_float4* albedo, const ptg_float4* normal_depth, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
+{
+    if(int r = bind(ctx)) return r;
+    if(!params || !radiance || !albedo || !normal_depth || !out_radiance) return fail(PTG_E_INVALID, "ptg_denoise: null argument");
+    const ptg_denoise_params P = *params;
+    if(P.iterations > 8) return fail(PTG_E_INVALID, "ptg_denoise: more than 8 iterations");
+    for(float s: {P.sigma_color, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor})
+        if(!(s > 0.0f) || !std::isfinite(s)) return fail(PTG_E_INVALID, "ptg_denoise: sigmas and albedo_floor must be positive and finite");
+    if(uint64_t(w) * h == 0) return PTG_OK;
+    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
+    const uint32_t n = w * h;
+    const float4* rad = reinterpret_cast<const float4*>(radiance);
+    const float4* alb = reinterpret_cast<const float4*>(albedo);
+    float4* out = reinterpret_cast<float4*>(out_radiance);
+    if(P.iterations == 0)
+    {   // the input bits, unchanged
+        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+        if(out_bgra)
+        {
+            hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, out, reinterpret_cast<uchar4*>(out_bgra));
+            PTG_HIP(hipGetLastError());
+        }
+        return PTG_OK;
+    }
+    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
+    float4* cur = ctx->dn_a.as<float4>();
+    float4* nxt = ctx->dn_b.as<float4>();
+    hipLaunchKernelGGL(k_dn_demodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, rad, alb, cur);
+    PTG_HIP(hipGetLastError());
+    DenoiseStep a;
+    a.w = w; a.h = h;
+    a.var_albedo = P.sigma_albedo * P.sigma_albedo;
+    a.var_normal = P.sigma_normal * P.sigma_normal;
+    a.var_depth = P.sigma_depth * P.sigma_depth;
+    for(uint32_t k = 0; k < P.iterations; ++k)
+    {
+        a.step = 1u << k;
+        const float sc = P.sigma_color * (1.0f / float(1u << k));   // sigma_color * 2^-k
+        a.var_color = sc * sc;
+        hipLaunchKernelGGL(k_dn_atrous, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, a, cur, alb,
+                           reinterpret_cast<const float4*>(normal_depth), nxt);
+        PTG_HIP(hipGetLastError());
+        std::swap(cur, nxt);
+    }
+    hipLaunchKernelGGL(k_dn_remodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, cur, alb, out,
+                       reinterpret_cast<uchar4*>(out_bgra));
+    PTG_HIP(hipGetLastError());
     return PTG_OK;
 }
 

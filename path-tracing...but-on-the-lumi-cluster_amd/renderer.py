@@ -130,6 +130,57 @@ class GpuRenderer:
                 "ptg_trace_rays")
         return hits
 
+    def camera_rays(self, cfg, xy: np.ndarray, sample_index: np.ndarray):
+        """The first ray of each (pixel, sample) pair (ptg_camera_rays):
+        (rays float32 [n, 8] in trace_rays' layout, subframe uint32 [n])."""
+        xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+        js = np.ascontiguousarray(sample_index, dtype=np.int32).reshape(-1)
+        rays = np.zeros((len(js), 8), np.float32)
+        sub = np.zeros(len(js), np.uint32)
+        N.check(N.lib().ptg_camera_rays(self._ctx, C.byref(cfg), len(js), xy.ctypes.data, js.ctypes.data,
+                                        rays.ctypes.data, sub.ctypes.data), "ptg_camera_rays")
+        return rays, sub
+
+    # -- first-hit features and the denoiser ----------------------------------
+    def render_features(self, cfg: N.RenderConfig, rect=None, samples=None):
+        """First-hit feature buffers over `rect` and sample range `samples`
+        (defaults as render()): (albedo+coverage, normal+depth), two float32
+        [h, w, 4] torch tensors on this GPU.  Asynchronous."""
+        import torch
+        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
+        dev = torch.device("cuda", self.device)
+        albedo = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        normal_depth = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        N.check(N.lib().ptg_render_features(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(albedo),
+                                            _ptr(normal_depth)), "ptg_render_features")
+        return albedo, normal_depth
+
+    def denoise(self, radiance, albedo, normal_depth, params=None, want_bgra=True, out_radiance=None):
+        """ptg_denoise over device float32 [h, w, 4] tensors: (denoised
+        radiance, bgra uint8 [h, w, 4] or None).  `out_radiance` may be
+        `radiance` itself.  Asynchronous."""
+        import torch
+        from .denoise import DenoiseParams
+        p = params if params is not None else DenoiseParams.default()
+        h, w = radiance.shape[:2]
+        for t in (radiance, albedo, normal_depth):
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        if out_radiance is None:
+            out_radiance = torch.empty_like(radiance)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
+        N.check(N.lib().ptg_denoise(self._ctx, w, h, C.byref(p), _ptr(radiance), _ptr(albedo), _ptr(normal_depth),
+                                    _ptr(out_radiance), _ptr(bgra)), "ptg_denoise")
+        return out_radiance, bgra
+
+    def render_denoised(self, cfg: N.RenderConfig, params=None):
+        """render + render_features + denoise of the whole image: (bgra,
+        denoised radiance).  Asynchronous."""
+        _, acc = self.render(cfg, want_accum=True)
+        albedo, normal_depth = self.render_features(cfg)
+        out, bgra = self.denoise(acc, albedo, normal_depth, params, want_bgra=True, out_radiance=acc)
+        return bgra, out
+
     def tonemap_device(self, colors, out_bgra):
         """tonemap_pixel over a device float32 [..., 4] tensor into a device
         uint8 [..., 4] tensor (ptg_tonemap_device; asynchronous)."""
