@@ -28,6 +28,7 @@
 #include <memory>
 #include <tuple>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <unordered_map>
 #include <unordered_set>
@@ -263,10 +264,42 @@ constexpr uint32_t kBands = 1024;   // XCD bands of a walk queue: a multiple of 
 // a chunk's device counters: per round the queue / NEE list lengths (2 words,
 // plus 4 spare), the hit / sky list lengths (2), the redo list lengths (2)
 constexpr uint32_t kCountWords(uint32_t rounds) { return 4 * (rounds + 2) + 2 * rounds; }
-// a chunk pipeline's state bytes per queued path, as render_map carves them:
-// 2 ping-pong PathSoA halves of 9 x 16 B, 2 TraceOut sets (hit 16 B, bary
-// 8 B, shadow 4 B), 5 lists of 4 B (2 NEE lists, hit, sky, redo)
+// a chunk pipeline's state bytes per queued path: 2 ping-pong PathSoA halves
+// of 9 x 16 B, 2 TraceOut sets (hit 16 B, bary 8 B, shadow 4 B), 5 lists of
+// 4 B (2 NEE lists, hit, sky, redo); the chunk sizing budgets with it and
+// carve_slot_state checks it against the fields it hands out
 constexpr size_t kStateBytesPerPath = 2 * 9 * 16 + 2 * (16 + 8 + 4) + 5 * 4;
+// the path state of one chunk pipeline (ptg_context::Slot::state)
+struct SlotState {
+    PathSoA S[2];
+    TraceOut trs[2];   // per round parity: the sky kernel of round r reads its set while round r+1 writes the other
+    uint32_t* lists[2];                 // NEE lists, by round parity
+    uint32_t *hit_list, *sky_list;      // this round's paths by shading kernel
+    uint32_t* redo_hit;                 // surface paths to shade again with MathExact
+    uint32_t* counts;                   // kCountWords(rounds) words
+};
+constexpr size_t slot_state_bytes(size_t M, uint32_t rounds) { return M * kStateBytesPerPath + kCountWords(rounds) * 4 + 256; }
+// Cuts a slot's state buffer (slot_state_bytes(M, rounds) at `base`) into its
+// arrays of M entries, in this order in memory, the counts behind them.
+// False if the fields' bytes per path are not kStateBytesPerPath.
+inline bool carve_slot_state(char* base, size_t M, SlotState& t)
+{
+    size_t per_path = 0;
+    auto take = [&](auto*& field) {
+        using T = std::remove_reference_t<decltype(*field)>;
+        field = reinterpret_cast<T*>(base + per_path * M);
+        per_path += sizeof(T);
+    };
+    for(PathSoA& s: t.S)
+    {
+        take(s.meta); take(s.seed); take(s.ray_o); take(s.ray_d); take(s.att);
+        take(s.contrib); take(s.batt); take(s.nee_c); take(s.nee_d);
+    }
+    for(TraceOut& o: t.trs) { take(o.hit); take(o.bary); take(o.shadow); }
+    take(t.lists[0]); take(t.lists[1]); take(t.hit_list); take(t.sky_list); take(t.redo_hit);
+    t.counts = reinterpret_cast<uint32_t*>(base + per_path * M);
+    return per_path == kStateBytesPerPath;
+}
 constexpr uint32_t kRedoGrid = 16;   // blocks of the MathExact shading passes (grid-stride over a short list)
 
 // Walk statistics of the counting build (per walk kind, see WalkStats): how
@@ -1075,7 +1108,7 @@ struct ptg_context {
     std::vector<ptg_subframe> host_subframes;
     bool frame_ready = false;
     // render workspace
-    DevBuf samples, acc, tmp_a, tmp_b, tmp_c, counters;
+    DevBuf acc, tmp_a, tmp_b, tmp_c, counters;
     DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
     DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
     DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
@@ -1097,47 +1130,36 @@ struct ptg_context {
     // together, so a default render leaves most of the GPU to other tenants;
     // 2^28 (~71%) is 1-3% faster on a GPU the renderer owns alone.
     uint32_t chunk_log2 = 27;
-    DevBuf wf_state;
     uint64_t kind_counters[6][8] = {};
     uint64_t walk_stats[2][8] = {};        // counting builds: WalkStat tallies of the closest-hit / any-hit walks
     uint64_t redo_stats[kRedoWords] = {};  // counting builds: the certified shading's redo tallies (tally_redo)
-    // second stream for the sky kernels + the events that order it with `stream`
-    hipStream_t side = nullptr;
-    hipEvent_t ev_main = nullptr, ev_side = nullptr;
     // Wavefront chunk pipelines ("slots").  With two slots, consecutive
     // chunks run concurrently on their own stream pairs and buffers, so one
     // chunk's round-0 walk and shade overlap the other's sky and shadow
     // kernels; k_accumulate still folds the chunks in sample order, each on
-    // its chunk's slot stream, chained by events across the slots (render_map).
-    // Slot 0 is the context's own stream pair and buffers.
+    // its chunk's slot stream, chained by events across the slots (fold_chunk).
+    // The megakernel and concurrency levels 0 / 1 use slot 0 alone.
     struct Slot {
+        // main: camera, closest-hit walk, classify, shade, fold; side: shadow
+        // walk and sky.  Slot 0 has no main stream of its own: its chunks run
+        // on the caller's stream (main_of)
         hipStream_t main = nullptr, side = nullptr;
-        hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_acc = nullptr;   // ev_acc: its last fold done
-        DevBuf own_state, own_samples;
-        DevBuf* state = nullptr;
-        DevBuf* samples = nullptr;
+        // the events that order main and side; ev_acc: the slot's last fold done
+        hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_acc = nullptr;
+        DevBuf state, samples;   // path state (SlotState), the chunk's per-sample results
     };
-    static constexpr uint32_t kMaxSlots = kWfSlots;
-    Slot slot[kMaxSlots];
-    uint32_t nslots = 1;
+    Slot slot[kWfSlots];
+    hipStream_t main_of(uint32_t k) const { return k ? slot[k].main : stream; }
     uint32_t concurrency = 2;              // ptg_set_concurrency
     hipEvent_t ev_render_start = nullptr;
     ~ptg_context()
     {
-        if(ev_main) (void)hipEventDestroy(ev_main);
-        if(ev_side) (void)hipEventDestroy(ev_side);
-        if(side) (void)hipStreamDestroy(side);
-        for(uint32_t k = 1; k < kMaxSlots; ++k)
+        for(Slot& b: slot)
         {
-            Slot& b = slot[k];
-            for(hipEvent_t e: {b.ev_main, b.ev_side})
+            for(hipEvent_t e: {b.ev_main, b.ev_side, b.ev_acc})
                 if(e) (void)hipEventDestroy(e);
             for(hipStream_t st: {b.main, b.side})
                 if(st) (void)hipStreamDestroy(st);
-        }
-        for(uint32_t k = 0; k < kMaxSlots; ++k)
-        {
-            if(slot[k].ev_acc) (void)hipEventDestroy(slot[k].ev_acc);
         }
         if(ev_render_start) (void)hipEventDestroy(ev_render_start);
         for(hipEvent_t e: ev_start) (void)hipEventDestroy(e);
@@ -1145,15 +1167,12 @@ struct ptg_context {
     }
 
     // Wait for everything queued on the context's streams: the caller's
-    // stream, the second streams and the extra chunk pipeline.
+    // stream and every slot's own.
     hipError_t drain() const
     {
-        for(hipStream_t st: {stream, side})
-            if(hipError_t e = hipStreamSynchronize(st)) return e;
-        for(uint32_t k = 1; k < kMaxSlots; ++k)
-            for(hipStream_t st: {slot[k].main, slot[k].side})
-                if(st)
-                    if(hipError_t e = hipStreamSynchronize(st)) return e;
+        for(uint32_t k = 0; k < kWfSlots; ++k)
+            for(hipStream_t st: {main_of(k), slot[k].side})
+                if(hipError_t e = hipStreamSynchronize(st)) return e;
         return hipSuccess;
     }
     // Grow a workspace buffer.  Growing frees the old allocation, which work
@@ -1231,389 +1250,12 @@ int check_cfg(const ptg_context* ctx, const ptg_render_config* cfg, uint32_t sam
 // separately and count into K_SHADE)
 enum Kind : int { K_MEGA = 0, K_EXTEND = 1, K_SHADOW = 2, K_SHADE = 3, K_CAMERA = 4, K_ACCUM = 5, K_KINDS = 6,
                   K_SKY = 6, K_CLASSIFY = 7 };
-// counting builds: 8 work counters per kind, then WS_COUNT walk statistics
-// for the closest-hit and the any-hit walk
-// counting builds' device counters: 8 per kernel kind, the walk statistics,
-// then the certified shading's redo tallies (kRedoWords, tally_redo)
+// counting builds' device counters: 8 per kernel kind, the walk statistics
+// (WS_COUNT each for the closest-hit and the any-hit walk), then the
+// certified shading's redo tallies (kRedoWords, tally_redo)
 constexpr int kCounterWords = K_KINDS * 8 + 2 * WS_COUNT + kRedoWords;
 
-int timed_begin(ptg_context* ctx, int kind, hipStream_t st = nullptr);
-int timed_end(ptg_context* ctx, hipStream_t st = nullptr);
-
-// Render the pixels of `pm` for samples [j0, j1): per chunk of samples, the
-// path kernels write one float4 per (pixel, sample); k_accumulate folds the
-// chunk into the running per-pixel sum in sample order.
-int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
-               ptg_float4* out_accum, ptg_uchar4* out_bgra)
-{
-    if(pm.npix == 0) return PTG_OK;
-    if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
-    const bool wf = ctx->pipeline == 0;
-    if(!wf && ctx->stack_bound >= PrivStack::kCap)
-        return fail(PTG_E_RANGE, "the megakernel's walk stack holds " + std::to_string(PrivStack::kCap) +
-                                     " entries, this frame's BVHs need " + std::to_string(ctx->stack_bound));
-    // samples per chunk: megakernel <= 1 GiB of results; wavefront ~16 M live paths
-    // Wavefront chunks are as large as HBM allows (capped at 35% of it): every
-    // bounce round then launches over a long queue, so the walk and shade
-    // launches run at full occupancy with short tails.  2^28 paths = 93 GB.
-    // wavefront chunk pipelines: slot 0 is the context's stream pair and buffers
-    const uint32_t nslots = (wf && ctx->concurrency >= 2) ? ctx->nslots : 1u;
-    ptg_context::Slot* slots = ctx->slot;
-    slots[0].main = ctx->stream;
-    slots[0].side = ctx->side;
-    slots[0].ev_main = ctx->ev_main;
-    slots[0].ev_side = ctx->ev_side;
-    slots[0].state = &ctx->wf_state;
-    slots[0].samples = &ctx->samples;
-    for(uint32_t k = 1; k < ptg_context::kMaxSlots; ++k)
-    {
-        slots[k].state = &slots[k].own_state;
-        slots[k].samples = &slots[k].own_samples;
-    }
-    size_t target = (size_t(1) << 30) / sizeof(float4);
-    if(wf)
-    {
-        size_t free_b = 0, total_b = 0;
-        PTG_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t per_path = kStateBytesPerPath + sizeof(float4);   // + the path's per-sample result
-        // a slot's share of HBM, but never more than what is actually free (other
-        // tenants, torch's cache): buffers this context already holds count as free
-        size_t held = 0;
-        for(uint32_t k = 0; k < nslots; ++k)
-            held += slots[k].state->bytes + slots[k].samples->bytes;
-        const size_t share = total_b / 100 * (nslots > 2 ? ctx->hbm_pct * 2 / nslots : ctx->hbm_pct);
-        const size_t avail = (free_b + held) / 100 * 85 / nslots;
-        target = std::max<size_t>(size_t(1) << 16, std::min(size_t(1) << ctx->chunk_log2, std::min(share, avail) / per_path));
-    }
-    // equal chunks of whole motion-blur groups (multiples of 8 samples), each <= target paths
-    const uint32_t span = j1 - j0;
-    const uint32_t max_chunk = std::max<uint32_t>(8, uint32_t(std::min<size_t>(target / size_t(pm.npix), span)) & ~7u);
-    uint32_t nchunks = (span + max_chunk - 1) / max_chunk;
-    if(nslots > 1 && span >= 16u)
-        nchunks = (std::max(nchunks, nslots) + nslots - 1) / nslots * nslots;   // whole rounds over the slots
-    uint32_t chunk = std::min<uint32_t>(span, ((span + nchunks - 1) / nchunks + 7) & ~7u);
-    const size_t M = size_t((pm.npix + 7) / 8) * ((chunk + 7) / 8) * 64;   // lanes per chunk (upper bound)
-    if(M >= (1ull << 31)) return fail(PTG_E_RANGE, "chunk too large");
-    for(uint32_t k = 0; k < nslots; ++k)
-        PTG_HIP(ctx->grow(*slots[k].samples, size_t(pm.npix) * chunk * sizeof(float4)));
-    PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
-    unsigned long long* cnt_dev = nullptr;
-    if(ctx->counting)
-    {
-        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
-        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
-        cnt_dev = ctx->counters.as<unsigned long long>();
-    }
-    const uint32_t rounds = cfg->max_bounces + 1;
-    // path state of a slot: 2 x 9 records of 16 B per path, + trace outputs + NEE lists
-    struct SlotState {
-        PathSoA S[2];
-        TraceOut trs[2] = {};   // per round parity: the sky kernel of round r reads its set while round r+1 writes the other
-        uint32_t* lists[2] = {nullptr, nullptr};
-        uint32_t *hit_list = nullptr, *sky_list = nullptr;   // this round's paths by shading kernel
-        uint32_t* redo_hit = nullptr;   // surface paths to shade again with MathExact
-        uint32_t* counts = nullptr;
-    } st[ptg_context::kMaxSlots];
-    if(wf)
-        for(uint32_t k = 0; k < nslots; ++k)
-        {
-            const size_t rec = M * 16;
-            PTG_HIP(ctx->grow(*slots[k].state, M * kStateBytesPerPath + kCountWords(rounds) * 4 + 256));
-            char* b = slots[k].state->as<char>();
-            SlotState& t = st[k];
-            for(int h = 0; h < 2; ++h)
-            {
-                t.S[h].meta = reinterpret_cast<uint4*>(b); b += rec;
-                t.S[h].seed = reinterpret_cast<uint4*>(b); b += rec;
-                t.S[h].ray_o = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].ray_d = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].att = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].contrib = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].batt = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].nee_c = reinterpret_cast<float4*>(b); b += rec;
-                t.S[h].nee_d = reinterpret_cast<float4*>(b); b += rec;
-            }
-            for(TraceOut& o: t.trs)
-            {
-                o.hit = reinterpret_cast<uint4*>(b); b += M * 16;
-                o.bary = reinterpret_cast<float2*>(b); b += M * 8;
-                o.shadow = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            }
-            t.lists[0] = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            t.lists[1] = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            t.hit_list = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            t.sky_list = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            t.redo_hit = reinterpret_cast<uint32_t*>(b); b += M * 4;
-            t.counts = reinterpret_cast<uint32_t*>(b);
-        }
-    if(nslots > 1)
-    {   // the other slot and the accumulation stream start after what the caller queued
-        PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
-        for(uint32_t k = 1; k < nslots; ++k)
-            PTG_HIP(hipStreamWaitEvent(slots[k].main, ctx->ev_render_start, 0));
-    }
-    const DevScene sc = ctx->scene_args(cfg);
-    // walk stack spill areas: one per (chunk pipeline, walk kind), since up to
-    // four walk launches run at once; stack_bound entries per walk lane
-    const size_t spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
-    if(wf) PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * nslots * spill_region) * sizeof(uint2)));
-    auto walk_scene = [&](uint32_t slot, int kind) {
-        DevScene w = sc;
-        w.spill = ctx->spill.as<uint2>() + (2 * slot + uint32_t(kind)) * spill_region;
-        return w;
-    };
-    const uint32_t persistent = ctx->persistent_blocks;
-    const bool overlap = wf && ctx->side != nullptr && ctx->concurrency >= 1;
-    auto cnt_for = [&](int kind) { return cnt_dev ? cnt_dev + 8 * kind : nullptr; };
-    auto ws_for = [&](bool any) { return cnt_dev ? cnt_dev + 8 * K_KINDS + (any ? WS_COUNT : 0) : nullptr; };
-    unsigned long long* const redo_tally = cnt_dev ? cnt_dev + 8 * K_KINDS + 2 * WS_COUNT : nullptr;
-    // The chunk plan: (first sample, samples, slot), in sample order (the
-    // order the chunks are folded): equal chunks dealt round-robin.
-    // PTG_STAGGER builds, with two slots: staggered - slot 1 starts and ends with half a chunk,
-    // so the two pipelines never change chunks at the same moment (a change
-    // runs the previous chunk's fold and the next chunk's camera kernel, with
-    // no walk of that slot in flight: when both slots changed together the
-    // GPU ran no walk for ~8 ms, profiles/r06c_timeline/).  The sample ranges
-    // follow the chunks' expected completion order (equal cost per sample),
-    // so each slot's next chunk finds its previous chunk already folded.
-    struct Piece { uint32_t j, n, slot; };
-    std::vector<Piece> plan;
-#ifndef PTG_STAGGER
-#define PTG_STAGGER 0   // 1: the staggered plan (measured 1-3% slower: its half chunks' rounds cost more than the gap they remove)
-#endif
-    if(PTG_STAGGER && nslots == 2 && chunk >= 16 && chunk % 16 == 0 && span > chunk)
-    {
-        struct Nominal { uint64_t done; uint32_t slot, n; };
-        std::vector<Nominal> nom;
-        // each slot takes half of the span; slot 1's first piece is half a chunk
-        const uint32_t span1 = (span / 2) & ~7u, span0 = span - span1;
-        uint64_t t = 0;
-        for(uint32_t left = span0; left > 0;)
-        {
-            const uint32_t n = std::min(chunk, left);
-            t += n;
-            nom.push_back({t, 0u, n});
-            left -= n;
-        }
-        t = 0;
-        for(uint32_t left = span1, first = 1; left > 0; first = 0)
-        {
-            const uint32_t n = std::min(first ? chunk / 2 : chunk, left);
-            t += n;
-            nom.push_back({t, 1u, n});
-            left -= n;
-        }
-        std::stable_sort(nom.begin(), nom.end(), [](const Nominal& a, const Nominal& b) {
-            return a.done < b.done || (a.done == b.done && a.slot < b.slot); });
-        uint32_t j = j0;
-        for(const Nominal& x: nom)
-        {
-            if(j >= j1) break;
-            const uint32_t n = std::min(x.n, j1 - j);
-            plan.push_back({j, n, x.slot});
-            j += n;
-        }
-        if(j != j1) plan.clear();   // (never: the pieces cover span0 + span1 = span)
-    }
-    if(plan.empty())
-        for(uint32_t j = j0, k = 0; j < j1; j += chunk, ++k) plan.push_back({j, std::min(chunk, j1 - j), k % nslots});
-    // Folds (k_accumulate: the chunks' samples into the running per-pixel
-    // sums, chunks in sample order) run on the chunk's own slot stream right
-    // after the chunk; a fold whose predecessor ran on the other slot first
-    // waits for that fold's event.  (A separate accumulation stream shared a
-    // hardware queue with slot 0's stream - HIP maps five streams onto
-    // GPU_MAX_HW_QUEUES = 4 queues - so a fold waiting for slot 1's chunk
-    // blocked slot 0's next launches behind it: profiles/r06c_timeline/.)
-    // A slot's next chunk then reuses its samples buffer after its fold in
-    // stream order, with no event at all.
-    uint32_t prev_slot = 0xFFFFFFFFu;
-    auto fold = [&](const Piece& pf) -> int {
-        ptg_context::Slot& sl = slots[pf.slot];
-        const int first = pf.j == j0, last = pf.j + pf.n >= j1;
-        const hipStream_t as = sl.main;
-        if(nslots > 1 && prev_slot != 0xFFFFFFFFu && prev_slot != pf.slot)
-            PTG_HIP(hipStreamWaitEvent(as, slots[prev_slot].ev_acc, 0));
-        if(int r = timed_begin(ctx, K_ACCUM, as)) return r;
-        hipLaunchKernelGGL(k_accumulate, dim3(grid_for(pm.npix)), dim3(kBlock), 0, as, pm, pf.n,
-                           sl.samples->as<float4>(), ctx->acc.as<float4>(), first, last, (float)cfg->samples_per_pixel,
-                           reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra));
-        PTG_HIP(hipGetLastError());
-        if(int r = timed_end(ctx, as)) return r;
-        if(nslots > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
-        prev_slot = pf.slot;
-        return PTG_OK;
-    };
-    for(const Piece& pc: plan)
-    {
-        const uint32_t j = pc.j, nj = pc.n, si = pc.slot;
-        ptg_context::Slot& sl = slots[si];
-        SlotState& sst = st[si];
-        const DevScene sc_ext = walk_scene(si, 0), sc_sh = walk_scene(si, 1);
-        PathSoA* S = sst.S;
-        TraceOut* trs = sst.trs;
-        uint32_t** lists = sst.lists;
-        uint32_t* hit_list = sst.hit_list;
-        uint32_t* sky_list = sst.sky_list;
-        uint32_t* counts = sst.counts;
-        const hipStream_t ms = sl.main;
-        const size_t lanes = size_t((pm.npix + 7) / 8) * ((nj + 7) / 8) * 64;
-        float4* out = sl.samples->as<float4>();
-        if(!wf)
-        {
-            if(int r = timed_begin(ctx, K_MEGA, ms)) return r;
-            if(ctx->counting)
-                hipLaunchKernelGGL(k_trace<true>, dim3(grid_for(lanes)), dim3(kBlock), 0, ms, sc, pm, j, nj, out,
-                                   cnt_for(K_MEGA));
-            else
-                hipLaunchKernelGGL(k_trace<false>, dim3(grid_for(lanes)), dim3(kBlock), 0, ms, sc, pm, j, nj, out,
-                                   nullptr);
-            PTG_HIP(hipGetLastError());
-            if(int r = timed_end(ctx, ms)) return r;
-        }
-        else
-        {
-            PTG_HIP(hipMemsetAsync(counts, 0, kCountWords(rounds) * sizeof(uint32_t), ms));
-            const dim3 grid(std::max<uint32_t>(1, std::min<uint32_t>(persistent, grid_for(lanes))));
-            if(int r = timed_begin(ctx, K_CAMERA, ms)) return r;
-            if(ctx->counting)
-                hipLaunchKernelGGL(k_wf_camera<true>, grid, dim3(kBlock), 0, ms, sc, pm, j, nj, uint32_t(lanes),
-                                   S[0], counts, out, cnt_for(K_CAMERA));
-            else
-                hipLaunchKernelGGL(k_wf_camera<false>, grid, dim3(kBlock), 0, ms, sc, pm, j, nj, uint32_t(lanes),
-                                   S[0], counts, out, nullptr);
-            PTG_HIP(hipGetLastError());
-            if(int r = timed_end(ctx, ms)) return r;
-            for(uint32_t r = 0; r < rounds; ++r)
-            {
-                const PathSoA& cur = S[r & 1];
-                const PathSoA& nxt = S[(r + 1) & 1];
-                const TraceOut& tr = trs[r & 1];
-                if(int e = timed_begin(ctx, K_EXTEND, ms)) return e;
-                if(ctx->counting)
-                    hipLaunchKernelGGL((k_wf_walk<false, true>), ctx->walk_grid[0], dim3(kBlock), ctx->walk_lds[0], ms, sc_ext,
-                                       cur, counts, r, nullptr, tr, ctx->walk_xcds[0], cnt_for(K_EXTEND), ws_for(false));
-                else
-                    hipLaunchKernelGGL((k_wf_walk<false, false>), ctx->walk_grid[0], dim3(kBlock), ctx->walk_lds[0], ms, sc_ext,
-                                       cur, counts, r, nullptr, tr, ctx->walk_xcds[0], nullptr, nullptr);
-                PTG_HIP(hipGetLastError());
-                if(int e = timed_end(ctx, ms)) return e;
-                // second stream: the previous round's sky kernel, then this round's
-                // shadow walk (independent of the closest-hit walk it runs beside)
-                const hipStream_t ss = overlap ? sl.side : ms;
-                if(r > 0)
-                {
-                    if(int e = timed_begin(ctx, K_SHADOW, ss)) return e;
-                    if(ctx->counting)
-                        hipLaunchKernelGGL((k_wf_walk<true, true>), ctx->walk_grid[1], dim3(kBlock), ctx->walk_lds[1], ss,
-                                           sc_sh, cur, counts, r, lists[r & 1], tr, ctx->walk_xcds[1], cnt_for(K_SHADOW),
-                                           ws_for(true));
-                    else
-                        hipLaunchKernelGGL((k_wf_walk<true, false>), ctx->walk_grid[1], dim3(kBlock), ctx->walk_lds[1], ss,
-                                           sc_sh, cur, counts, r, lists[r & 1], tr, ctx->walk_xcds[1], nullptr, nullptr);
-                    PTG_HIP(hipGetLastError());
-                    if(int e = timed_end(ctx, ss)) return e;
-                }
-                uint32_t* lc = counts + 2 * (rounds + 2) + 2 * r;   // this round's hit / sky list lengths
-                uint32_t* rc = counts + 4 * (rounds + 2) + 2 * r;   // this round's redo list lengths (hit, sky)
-                // classify/shade need the shadow results, the lists the previous sky
-                // kernel read, and the state set it read
-                if(overlap)
-                {
-                    PTG_HIP(hipEventRecord(sl.ev_side, sl.side));
-                    PTG_HIP(hipStreamWaitEvent(ms, sl.ev_side, 0));
-                }
-                if(int e = timed_begin(ctx, K_CLASSIFY, ms)) return e;
-                hipLaunchKernelGGL(k_wf_classify, grid, dim3(kBlock), 0, ms, counts, r, tr, hit_list, sky_list, lc);
-                PTG_HIP(hipGetLastError());
-                if(int e = timed_end(ctx, ms)) return e;
-                if(int e = timed_begin(ctx, K_SHADE, ms)) return e;
-                // the certified pass, then the exact pass over the paths it listed
-                if(ctx->counting)
-                    hipLaunchKernelGGL((k_wf_shade<true, ShadeMath>), grid, dim3(kBlock), 0, ms, sc, cur, nxt, counts, r, tr,
-                                       hit_list, lc, lists[(r + 1) & 1], trs[(r + 1) & 1].shadow, out, sst.redo_hit, rc,
-                                       cnt_for(K_SHADE), redo_tally);
-                else
-                    hipLaunchKernelGGL((k_wf_shade<false, ShadeMath>), grid, dim3(kBlock), 0, ms, sc, cur, nxt, counts, r,
-                                       tr, hit_list, lc, lists[(r + 1) & 1], trs[(r + 1) & 1].shadow, out, sst.redo_hit,
-                                       rc, nullptr, nullptr);
-                if constexpr(ShadeMath::kFast)
-                {
-                    if(ctx->counting)
-                        hipLaunchKernelGGL((k_wf_shade<true, MathExact>), dim3(kRedoGrid), dim3(kBlock), 0, ms, sc, cur,
-                                           nxt, counts, r, tr, sst.redo_hit, rc, lists[(r + 1) & 1],
-                                           trs[(r + 1) & 1].shadow, out, nullptr, nullptr, cnt_for(K_SHADE), nullptr);
-                    else
-                        hipLaunchKernelGGL((k_wf_shade<false, MathExact>), dim3(kRedoGrid), dim3(kBlock), 0, ms, sc, cur,
-                                           nxt, counts, r, tr, sst.redo_hit, rc, lists[(r + 1) & 1],
-                                           trs[(r + 1) & 1].shadow, out, nullptr, nullptr, nullptr, nullptr);
-                }
-                PTG_HIP(hipGetLastError());
-                if(int e = timed_end(ctx, ms)) return e;
-                // escaped rays retire without feeding the next round: their
-                // double-precision atmosphere runs on the second stream, overlapping
-                // the next round's latency-bound walks (started beside shade instead,
-                // the two compete for registers: 9% slower on frame 0)
-                if(overlap)
-                {
-                    PTG_HIP(hipEventRecord(sl.ev_main, ms));
-                    PTG_HIP(hipStreamWaitEvent(sl.side, sl.ev_main, 0));
-                }
-                if(int e = timed_begin(ctx, K_SKY, ss)) return e;
-                if(ctx->counting)
-                    hipLaunchKernelGGL(k_wf_sky<true>, grid, dim3(kBlock), 0, ss, sc, cur, tr, r, sky_list, lc, out,
-                                       cnt_for(K_SHADE));
-                else
-                    hipLaunchKernelGGL(k_wf_sky<false>, grid, dim3(kBlock), 0, ss, sc, cur, tr, r, sky_list, lc, out, nullptr);
-                PTG_HIP(hipGetLastError());
-                if(int e = timed_end(ctx, ss)) return e;
-            }
-            if(overlap)
-            {   // join before accumulate
-                PTG_HIP(hipEventRecord(sl.ev_side, sl.side));
-                PTG_HIP(hipStreamWaitEvent(ms, sl.ev_side, 0));
-            }
-        }
-        if(int r = fold(pc)) return r;
-    }
-    if(nslots > 1 && prev_slot != 0xFFFFFFFFu && slots[prev_slot].main != ctx->stream)
-        PTG_HIP(hipStreamWaitEvent(ctx->stream, slots[prev_slot].ev_acc, 0));   // the caller's stream sees the whole render
-#if PTG_DEBUG
-    {
-        uint32_t dbg[kDebugSlots];
-        PTG_HIP(hipStreamSynchronize(ctx->stream));
-        PTG_HIP(hipMemcpy(dbg, ctx->debug.p, sizeof(dbg), hipMemcpyDeviceToHost));
-        std::string bad;
-        static const char* names[kDebugSlots] = {"node record", "triangle", "instance", "NEE list", "shade list", "walk stack", "", ""};
-        for(uint32_t k = 0; k < kDebugSlots; ++k)
-            if(dbg[k]) bad += std::string(bad.empty() ? "" : ", ") + names[k] + " index out of range x" + std::to_string(dbg[k]);
-        if(!bad.empty())
-        {
-            PTG_HIP(hipMemset(ctx->debug.p, 0, sizeof(dbg)));
-            return fail(PTG_E_RANGE, "PTG_DEBUG: " + bad);
-        }
-    }
-#endif
-    if(ctx->counting)
-    {
-        unsigned long long host[kCounterWords];
-        PTG_HIP(hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-        PTG_HIP(hipStreamSynchronize(ctx->stream));
-        for(int k = 0; k < 2 * WS_COUNT; ++k) ctx->walk_stats[k / WS_COUNT][k % WS_COUNT] = host[K_KINDS * 8 + k];
-        for(int k = 0; k < kRedoWords; ++k) ctx->redo_stats[k] = host[K_KINDS * 8 + 2 * WS_COUNT + k];
-        for(int i = 0; i < 8; ++i)
-        {
-            ctx->last_counters[i] = 0;
-            for(int k = 0; k < K_KINDS; ++k)
-            {
-                ctx->kind_counters[k][i] = host[k * 8 + i];
-                ctx->last_counters[i] += host[k * 8 + i];
-            }
-        }
-    }
-    return PTG_OK;
-}
-
-int timed_begin(ptg_context* ctx, int kind, hipStream_t st)
+int timed_begin(ptg_context* ctx, int kind, hipStream_t st = nullptr)
 {
     if(!ctx->timing) return PTG_OK;
     if(ctx->ev_used == ctx->ev_start.size())
@@ -1630,11 +1272,322 @@ int timed_begin(ptg_context* ctx, int kind, hipStream_t st)
     return PTG_OK;
 }
 
-int timed_end(ptg_context* ctx, hipStream_t st)
+int timed_end(ptg_context* ctx, hipStream_t st = nullptr)
 {
     if(!ctx->timing) return PTG_OK;
     PTG_HIP(hipEventRecord(ctx->ev_stop[ctx->ev_used++], st ? st : ctx->stream));
     return PTG_OK;
+}
+
+// A launch of the render path: the kernel's counting instantiation in a
+// counting render, the plain one otherwise.  Both take the same arguments (a
+// plain render passes null counter pointers, RenderJob::cnt_for).
+template<typename... P, typename... A>
+void launch_counted(const ptg_context* ctx, hipStream_t st, dim3 grid, uint32_t lds, void (*counting)(P...),
+                    void (*plain)(P...), const A&... args)
+{
+    void (*const kernel)(P...) = ctx->counting ? counting : plain;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, args...);
+}
+
+// One timed launch of `kind` (launch_counted between timed_begin and
+// timed_end), its launch error checked.  A kernel without a counting
+// instantiation is passed twice.
+template<typename... P, typename... A>
+int launch(ptg_context* ctx, int kind, hipStream_t st, dim3 grid, uint32_t lds, void (*counting)(P...), void (*plain)(P...),
+           const A&... args)
+{
+    if(int r = timed_begin(ctx, kind, st)) return r;
+    launch_counted(ctx, st, grid, lds, counting, plain, args...);
+    PTG_HIP(hipGetLastError());
+    return timed_end(ctx, st);
+}
+
+// A render call's fixed parts, shared by the steps render_map is made of.
+struct RenderJob {
+    ptg_context* ctx;
+    const ptg_render_config* cfg;
+    PixelMap pm;
+    uint32_t j0, j1;                       // the sample range
+    float4* out_accum;
+    uchar4* out_bgra;
+    uint32_t pipelines = 1;                // chunk pipelines (slots) in use
+    uint32_t chunk = 0;                    // samples per chunk
+    size_t M = 0;                          // queue positions of a full chunk
+    uint32_t rounds = 0;                   // bounce rounds
+    bool overlap = false;                  // wavefront: shadow walk and sky on the slots' side streams
+    DevScene sc;
+    size_t spill_region = 0;               // walk stack spill entries per (slot, walk kind)
+    unsigned long long* cnt = nullptr;     // counting renders: the device counters
+    uint32_t prev_slot = 0xFFFFFFFFu;      // the slot of the last fold
+    SlotState st[kWfSlots];
+
+    unsigned long long* cnt_for(int kind) const { return cnt ? cnt + 8 * kind : nullptr; }
+    unsigned long long* ws_for(bool any) const { return cnt ? cnt + 8 * K_KINDS + (any ? WS_COUNT : 0) : nullptr; }
+    unsigned long long* redo_tally() const { return cnt ? cnt + 8 * K_KINDS + 2 * WS_COUNT : nullptr; }
+    // walk stack spill areas: one per (chunk pipeline, walk kind), since up to
+    // four walk launches run at once; stack_bound entries per walk lane
+    DevScene walk_scene(uint32_t slot, int kind) const
+    {
+        DevScene w = sc;
+        w.spill = ctx->spill.as<uint2>() + (2 * slot + uint32_t(kind)) * spill_region;
+        return w;
+    }
+    size_t lanes(uint32_t nj) const { return size_t((pm.npix + 7) / 8) * ((nj + 7) / 8) * 64; }
+};
+
+// A chunk: samples [j, j + n) on chunk pipeline `slot`.
+struct Piece { uint32_t j, n, slot; };
+
+// Chunk sizing: equal chunks of whole motion-blur groups (multiples of 8
+// samples), each at most `target` paths.  The megakernel's target is 1 GiB of
+// per-sample results.  Wavefront chunks are as large as HBM allows, up to
+// 2^chunk_log2 paths: every bounce round then launches over a long queue, so
+// the walk and shade launches run at full occupancy with short tails.
+int size_chunks(RenderJob& job, bool wf)
+{
+    ptg_context* ctx = job.ctx;
+    const uint32_t pipelines = job.pipelines;
+    size_t target = (size_t(1) << 30) / sizeof(float4);
+    if(wf)
+    {
+        size_t free_b = 0, total_b = 0;
+        PTG_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t per_path = kStateBytesPerPath + sizeof(float4);   // + the path's per-sample result
+        // a slot's share of HBM, but never more than what is actually free (other
+        // tenants, torch's cache): buffers this context already holds count as free
+        size_t held = 0;
+        for(uint32_t k = 0; k < pipelines; ++k)
+            held += ctx->slot[k].state.bytes + ctx->slot[k].samples.bytes;
+        const size_t share = total_b / 100 * (pipelines > 2 ? ctx->hbm_pct * 2 / pipelines : ctx->hbm_pct);
+        const size_t avail = (free_b + held) / 100 * 85 / pipelines;
+        target = std::max<size_t>(size_t(1) << 16, std::min(size_t(1) << ctx->chunk_log2, std::min(share, avail) / per_path));
+    }
+    const uint32_t span = job.j1 - job.j0;
+    const uint32_t max_chunk = std::max<uint32_t>(8, uint32_t(std::min<size_t>(target / size_t(job.pm.npix), span)) & ~7u);
+    uint32_t nchunks = (span + max_chunk - 1) / max_chunk;
+    if(pipelines > 1 && span >= 16u)
+        nchunks = (std::max(nchunks, pipelines) + pipelines - 1) / pipelines * pipelines;   // whole rounds over the slots
+    job.chunk = std::min<uint32_t>(span, ((span + nchunks - 1) / nchunks + 7) & ~7u);
+    job.M = job.lanes(job.chunk);
+    if(job.M >= (1ull << 31)) return fail(PTG_E_RANGE, "chunk too large");
+    return PTG_OK;
+}
+
+// The chunk plan, in sample order (the order the chunks are folded): equal
+// chunks dealt round-robin to the slots.
+std::vector<Piece> plan_chunks(const RenderJob& job)
+{
+    std::vector<Piece> plan;
+    for(uint32_t j = job.j0, k = 0; j < job.j1; j += job.chunk, ++k)
+        plan.push_back({j, std::min(job.chunk, job.j1 - j), k % job.pipelines});
+    return plan;
+}
+
+// One chunk of the megakernel: every path from camera to its last bounce in one launch.
+int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
+{
+    ptg_context* ctx = job.ctx;
+    return launch(ctx, K_MEGA, ctx->main_of(pc.slot), dim3(grid_for(job.lanes(pc.n))), 0, k_trace<true>, k_trace<false>, job.sc,
+                  job.pm, pc.j, pc.n, ctx->slot[pc.slot].samples.as<float4>(), job.cnt_for(K_MEGA));
+}
+
+// One chunk of the wavefront pipeline on its slot's streams: the camera
+// kernel, then per bounce round the closest-hit walk, the shadow walk of the
+// previous round's NEE rays, classify, shade and sky.
+int trace_chunk_wavefront(RenderJob& job, const Piece& pc)
+{
+    ptg_context* ctx = job.ctx;
+    ptg_context::Slot& sl = ctx->slot[pc.slot];
+    const SlotState& t = job.st[pc.slot];
+    const DevScene& sc = job.sc;
+    const DevScene sc_ext = job.walk_scene(pc.slot, 0), sc_sh = job.walk_scene(pc.slot, 1);
+    const uint32_t rounds = job.rounds;
+    uint32_t* counts = t.counts;
+    const hipStream_t ms = ctx->main_of(pc.slot);
+    // second stream: the previous round's sky kernel, then this round's
+    // shadow walk (independent of the closest-hit walk it runs beside)
+    const hipStream_t ss = job.overlap ? sl.side : ms;
+    auto side_after_main = [&]() -> int {
+        if(!job.overlap) return PTG_OK;
+        PTG_HIP(hipEventRecord(sl.ev_main, ms));
+        PTG_HIP(hipStreamWaitEvent(sl.side, sl.ev_main, 0));
+        return PTG_OK;
+    };
+    auto main_after_side = [&]() -> int {
+        if(!job.overlap) return PTG_OK;
+        PTG_HIP(hipEventRecord(sl.ev_side, sl.side));
+        PTG_HIP(hipStreamWaitEvent(ms, sl.ev_side, 0));
+        return PTG_OK;
+    };
+    const size_t lanes = job.lanes(pc.n);
+    float4* out = sl.samples.as<float4>();
+    PTG_HIP(hipMemsetAsync(counts, 0, kCountWords(rounds) * sizeof(uint32_t), ms));
+    const dim3 grid(std::max<uint32_t>(1, std::min<uint32_t>(ctx->persistent_blocks, grid_for(lanes))));
+    if(int e = launch(ctx, K_CAMERA, ms, grid, 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, pc.j, pc.n,
+                      uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA)))
+        return e;
+    for(uint32_t r = 0; r < rounds; ++r)
+    {
+        const PathSoA& cur = t.S[r & 1];
+        const PathSoA& nxt = t.S[(r + 1) & 1];
+        const TraceOut& tr = t.trs[r & 1];
+        uint32_t* nee_next = t.lists[(r + 1) & 1];
+        uint32_t* shadow_next = t.trs[(r + 1) & 1].shadow;
+        if(int e = launch(ctx, K_EXTEND, ms, ctx->walk_grid[0], ctx->walk_lds[0], k_wf_walk<false, true>,
+                          k_wf_walk<false, false>, sc_ext, cur, counts, r, nullptr, tr, ctx->walk_xcds[0],
+                          job.cnt_for(K_EXTEND), job.ws_for(false)))
+            return e;
+        if(r > 0)
+            if(int e = launch(ctx, K_SHADOW, ss, ctx->walk_grid[1], ctx->walk_lds[1], k_wf_walk<true, true>,
+                              k_wf_walk<true, false>, sc_sh, cur, counts, r, t.lists[r & 1], tr, ctx->walk_xcds[1],
+                              job.cnt_for(K_SHADOW), job.ws_for(true)))
+                return e;
+        uint32_t* lc = counts + 2 * (rounds + 2) + 2 * r;   // this round's hit / sky list lengths
+        uint32_t* rc = counts + 4 * (rounds + 2) + 2 * r;   // this round's redo list lengths (hit, sky)
+        // classify/shade need the shadow results, the lists the previous sky
+        // kernel read, and the state set it read
+        if(int e = main_after_side()) return e;
+        if(int e = launch(ctx, K_CLASSIFY, ms, grid, 0, k_wf_classify, k_wf_classify, counts, r, tr, t.hit_list, t.sky_list, lc))
+            return e;
+        // the certified pass, then the exact pass over the paths it listed: one timed interval
+        if(int e = timed_begin(ctx, K_SHADE, ms)) return e;
+        launch_counted(ctx, ms, grid, 0, k_wf_shade<true, ShadeMath>, k_wf_shade<false, ShadeMath>, sc, cur, nxt, counts, r, tr,
+                       t.hit_list, lc, nee_next, shadow_next, out, t.redo_hit, rc, job.cnt_for(K_SHADE), job.redo_tally());
+        if constexpr(ShadeMath::kFast)
+            launch_counted(ctx, ms, dim3(kRedoGrid), 0, k_wf_shade<true, MathExact>, k_wf_shade<false, MathExact>, sc, cur, nxt,
+                           counts, r, tr, t.redo_hit, rc, nee_next, shadow_next, out, nullptr, nullptr, job.cnt_for(K_SHADE),
+                           nullptr);
+        PTG_HIP(hipGetLastError());
+        if(int e = timed_end(ctx, ms)) return e;
+        // escaped rays retire without feeding the next round: their
+        // double-precision atmosphere runs on the second stream, overlapping
+        // the next round's latency-bound walks (started beside shade instead,
+        // the two compete for registers: 9% slower on frame 0)
+        if(int e = side_after_main()) return e;
+        if(int e = launch(ctx, K_SKY, ss, grid, 0, k_wf_sky<true>, k_wf_sky<false>, sc, cur, tr, r, t.sky_list, lc, out,
+                          job.cnt_for(K_SHADE)))
+            return e;
+    }
+    return main_after_side();   // join before the fold
+}
+
+// The fold of a chunk (k_accumulate: its samples into the running per-pixel
+// sums, chunks in sample order) runs on the chunk's own slot stream right
+// after the chunk; a fold whose predecessor ran on the other slot first
+// waits for that fold's event.  (A separate accumulation stream shared a
+// hardware queue with slot 0's stream - HIP maps five streams onto
+// GPU_MAX_HW_QUEUES = 4 queues - so a fold waiting for slot 1's chunk
+// blocked slot 0's next launches behind it: profiles/r06c_timeline/.)
+// A slot's next chunk then reuses its samples buffer after its fold in
+// stream order, with no event at all.
+int fold_chunk(RenderJob& job, const Piece& pc)
+{
+    ptg_context* ctx = job.ctx;
+    ptg_context::Slot& sl = ctx->slot[pc.slot];
+    const int first = pc.j == job.j0, last = pc.j + pc.n >= job.j1;
+    const hipStream_t as = ctx->main_of(pc.slot);
+    if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
+        PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
+    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate, k_accumulate, job.pm, pc.n,
+                      sl.samples.as<float4>(), ctx->acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
+                      job.out_accum, job.out_bgra))
+        return r;
+    if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
+    job.prev_slot = pc.slot;
+    return PTG_OK;
+}
+
+#if PTG_DEBUG
+// PTG_DEBUG builds: the render's out-of-range index tallies (waits for the render)
+int check_debug_tallies(ptg_context* ctx)
+{
+    uint32_t dbg[kDebugSlots];
+    PTG_HIP(hipStreamSynchronize(ctx->stream));
+    PTG_HIP(hipMemcpy(dbg, ctx->debug.p, sizeof(dbg), hipMemcpyDeviceToHost));
+    std::string bad;
+    static const char* names[kDebugSlots] = {"node record", "triangle", "instance", "NEE list", "shade list", "walk stack", "", ""};
+    for(uint32_t k = 0; k < kDebugSlots; ++k)
+        if(dbg[k]) bad += std::string(bad.empty() ? "" : ", ") + names[k] + " index out of range x" + std::to_string(dbg[k]);
+    if(bad.empty()) return PTG_OK;
+    PTG_HIP(hipMemset(ctx->debug.p, 0, sizeof(dbg)));
+    return fail(PTG_E_RANGE, "PTG_DEBUG: " + bad);
+}
+#endif
+
+// Counting renders: the device counters into the context (waits for the render).
+int read_counters(ptg_context* ctx)
+{
+    unsigned long long host[kCounterWords];
+    PTG_HIP(hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    PTG_HIP(hipStreamSynchronize(ctx->stream));
+    for(int k = 0; k < 2 * WS_COUNT; ++k) ctx->walk_stats[k / WS_COUNT][k % WS_COUNT] = host[K_KINDS * 8 + k];
+    for(int k = 0; k < kRedoWords; ++k) ctx->redo_stats[k] = host[K_KINDS * 8 + 2 * WS_COUNT + k];
+    for(int i = 0; i < 8; ++i)
+    {
+        ctx->last_counters[i] = 0;
+        for(int k = 0; k < K_KINDS; ++k)
+        {
+            ctx->kind_counters[k][i] = host[k * 8 + i];
+            ctx->last_counters[i] += host[k * 8 + i];
+        }
+    }
+    return PTG_OK;
+}
+
+// Render the pixels of `pm` for samples [j0, j1): per chunk of samples, the
+// path kernels write one float4 per (pixel, sample); k_accumulate folds the
+// chunk into the running per-pixel sum in sample order.
+int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
+               ptg_float4* out_accum, ptg_uchar4* out_bgra)
+{
+    if(pm.npix == 0) return PTG_OK;
+    if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
+    const bool wf = ctx->pipeline == 0;
+    if(!wf && ctx->stack_bound >= PrivStack::kCap)
+        return fail(PTG_E_RANGE, "the megakernel's walk stack holds " + std::to_string(PrivStack::kCap) +
+                                     " entries, this frame's BVHs need " + std::to_string(ctx->stack_bound));
+    RenderJob job{ctx, cfg, pm, j0, j1, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra)};
+    const uint32_t pipelines = job.pipelines = (wf && ctx->concurrency >= 2) ? kWfSlots : 1u;
+    job.rounds = cfg->max_bounces + 1;
+    job.overlap = wf && ctx->concurrency >= 1;
+    if(int r = size_chunks(job, wf)) return r;
+    for(uint32_t k = 0; k < pipelines; ++k)
+        PTG_HIP(ctx->grow(ctx->slot[k].samples, size_t(pm.npix) * job.chunk * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
+    if(ctx->counting)
+    {
+        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
+        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
+        job.cnt = ctx->counters.as<unsigned long long>();
+    }
+    if(wf)
+        for(uint32_t k = 0; k < pipelines; ++k)
+        {
+            PTG_HIP(ctx->grow(ctx->slot[k].state, slot_state_bytes(job.M, job.rounds)));
+            if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.st[k]))
+                return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
+        }
+    if(pipelines > 1)
+    {   // the other slots start after what the caller queued
+        PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
+        for(uint32_t k = 1; k < pipelines; ++k)
+            PTG_HIP(hipStreamWaitEvent(ctx->slot[k].main, ctx->ev_render_start, 0));
+    }
+    job.sc = ctx->scene_args(cfg);
+    job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
+    if(wf) PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * pipelines * job.spill_region) * sizeof(uint2)));
+    for(const Piece& pc: plan_chunks(job))
+    {
+        if(int r = wf ? trace_chunk_wavefront(job, pc) : trace_chunk_megakernel(job, pc)) return r;
+        if(int r = fold_chunk(job, pc)) return r;
+    }
+    if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
+        PTG_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[job.prev_slot].ev_acc, 0));   // the caller's stream sees the whole render
+#if PTG_DEBUG
+    if(int r = check_debug_tallies(ctx)) return r;
+#endif
+    return ctx->counting ? read_counters(ctx) : PTG_OK;
 }
 
 } // namespace
@@ -1708,23 +1661,15 @@ int ptg_context_create(int device, ptg_context** out)
     PTG_HIP(ctx->debug.reserve(kDebugSlots * sizeof(uint32_t)));
     PTG_HIP(hipMemset(ctx->debug.p, 0, kDebugSlots * sizeof(uint32_t)));
 #endif
-    PTG_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-    PTG_HIP(hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-    PTG_HIP(hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming));
-    for(uint32_t k = 1; k < kWfSlots; ++k)
-    {
-        ptg_context::Slot& b = ctx->slot[k];
-        PTG_HIP(hipStreamCreateWithFlags(&b.main, hipStreamNonBlocking));
-        PTG_HIP(hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
-        PTG_HIP(hipEventCreateWithFlags(&b.ev_main, hipEventDisableTiming));
-        PTG_HIP(hipEventCreateWithFlags(&b.ev_side, hipEventDisableTiming));
-    }
     for(uint32_t k = 0; k < kWfSlots; ++k)
     {
-        PTG_HIP(hipEventCreateWithFlags(&ctx->slot[k].ev_acc, hipEventDisableTiming));
+        ptg_context::Slot& b = ctx->slot[k];
+        if(k > 0) PTG_HIP(hipStreamCreateWithFlags(&b.main, hipStreamNonBlocking));   // slot 0: the caller's stream
+        PTG_HIP(hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
+        for(hipEvent_t* e: {&b.ev_main, &b.ev_side, &b.ev_acc})
+            PTG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     PTG_HIP(hipEventCreateWithFlags(&ctx->ev_render_start, hipEventDisableTiming));
-    ctx->nslots = kWfSlots;
     *out = ctx.release();
     return PTG_OK;
 }
@@ -2061,17 +2006,24 @@ int ptg_upload_from_scene(ptg_context* ctx, const ptg_scene* scene, int include_
                             v.links + 8 * v.static_node_count, v.static_node_count, v.node_count - v.static_node_count);
 }
 
+static int rect_map(const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, PixelMap& pm)
+{
+    if(uint64_t(x0) + w > cfg->width || uint64_t(y0) + h > cfg->height) return fail(PTG_E_RANGE, "rectangle outside the image");
+    pm = PixelMap{};
+    pm.tiles = 0;
+    pm.x0 = x0; pm.y0 = y0; pm.w = w; pm.h = h;
+    pm.img_w = cfg->width; pm.img_h = cfg->height;
+    pm.npix = w * h;
+    return PTG_OK;
+}
+
 int ptg_render(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_accum, ptg_uchar4* out_bgra)
 {
     if(int r = bind(ctx)) return r;
     if(int r = check_cfg(ctx, cfg, sample_end)) return r;
-    if(uint64_t(x0) + w > cfg->width || uint64_t(y0) + h > cfg->height) return fail(PTG_E_RANGE, "rectangle outside the image");
-    PixelMap pm{};
-    pm.tiles = 0;
-    pm.x0 = x0; pm.y0 = y0; pm.w = w; pm.h = h;
-    pm.img_w = cfg->width; pm.img_h = cfg->height;
-    pm.npix = w * h;
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra);
 }
 
@@ -2116,13 +2068,11 @@ int ptg_scatter_tiles(ptg_context* ctx, const ptg_render_config* cfg, uint32_t t
     return PTG_OK;
 }
 
-int ptg_path_trace_samples(ptg_context* ctx, const ptg_render_config* cfg, size_t n, const ptg_uint2* xy,
-                           const int32_t* sample_index, ptg_float4* out)
+// An explicit (pixel, sample) list: checked against the image and the frame's
+// subframes, then copied to tmp_a (xy) and tmp_b (sample indices).
+static int upload_sample_list(ptg_context* ctx, const ptg_render_config* cfg, size_t n, const ptg_uint2* xy,
+                              const int32_t* sample_index)
 {
-    if(int r = bind(ctx)) return r;
-    if(int r = check_cfg(ctx, cfg, 0)) return r;
-    if(!n) return PTG_OK;
-    if(!xy || !sample_index || !out || n >= (1u << 30)) return fail(PTG_E_INVALID, "ptg_path_trace_samples: bad arguments");
     int32_t jmax = 0;
     for(size_t i = 0; i < n; ++i)
     {
@@ -2131,12 +2081,23 @@ int ptg_path_trace_samples(ptg_context* ctx, const ptg_render_config* cfg, size_
     }
     if(uint64_t(jmax) / cfg->samples_per_motion_blur_step >= ctx->subframe_count)
         return fail(PTG_E_RANGE, "sample index beyond the frame's subframes");
-    if(ctx->stack_bound >= PrivStack::kCap) return fail(PTG_E_RANGE, "walk stack bound above the per-sample kernel's stack");
     PTG_HIP(ctx->grow(ctx->tmp_a, n * sizeof(uint2)));
     PTG_HIP(ctx->grow(ctx->tmp_b, n * sizeof(int32_t)));
-    PTG_HIP(ctx->grow(ctx->tmp_c, n * sizeof(float4)));
     PTG_HIP(hipMemcpyAsync(ctx->tmp_a.p, xy, n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
     PTG_HIP(hipMemcpyAsync(ctx->tmp_b.p, sample_index, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return PTG_OK;
+}
+
+int ptg_path_trace_samples(ptg_context* ctx, const ptg_render_config* cfg, size_t n, const ptg_uint2* xy,
+                           const int32_t* sample_index, ptg_float4* out)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, 0)) return r;
+    if(!n) return PTG_OK;
+    if(!xy || !sample_index || !out || n >= (1u << 30)) return fail(PTG_E_INVALID, "ptg_path_trace_samples: bad arguments");
+    if(int r = upload_sample_list(ctx, cfg, n, xy, sample_index)) return r;
+    if(ctx->stack_bound >= PrivStack::kCap) return fail(PTG_E_RANGE, "walk stack bound above the per-sample kernel's stack");
+    PTG_HIP(ctx->grow(ctx->tmp_c, n * sizeof(float4)));
     hipLaunchKernelGGL(k_sample_list, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(cfg), uint32_t(n),
                        ctx->tmp_a.as<uint2>(), ctx->tmp_b.as<int32_t>(), ctx->tmp_c.as<float4>());
     PTG_HIP(hipGetLastError());
@@ -2208,21 +2169,10 @@ int ptg_camera_rays(ptg_context* ctx, const ptg_render_config* cfg, size_t n, co
     if(int r = check_cfg(ctx, cfg, 0)) return r;
     if(!n) return PTG_OK;
     if(!xy || !sample_index || !rays || !subframe || n >= (1u << 28)) return fail(PTG_E_INVALID, "ptg_camera_rays: bad arguments");
-    int32_t jmax = 0;
-    for(size_t i = 0; i < n; ++i)
-    {
-        jmax = std::max(jmax, sample_index[i]);
-        if(xy[i].x >= cfg->width || xy[i].y >= cfg->height) return fail(PTG_E_RANGE, "pixel outside the image");
-    }
-    if(uint64_t(jmax) / cfg->samples_per_motion_blur_step >= ctx->subframe_count)
-        return fail(PTG_E_RANGE, "sample index beyond the frame's subframes");
-    PTG_HIP(ctx->grow(ctx->tmp_a, n * sizeof(uint2)));
-    PTG_HIP(ctx->grow(ctx->tmp_b, n * sizeof(int32_t)));
+    if(int r = upload_sample_list(ctx, cfg, n, xy, sample_index)) return r;
     PTG_HIP(ctx->grow(ctx->tmp_c, n * 36));            // n rays of 8 floats, then n subframe indices
     float* d_rays = ctx->tmp_c.as<float>();
     uint32_t* d_sub = reinterpret_cast<uint32_t*>(d_rays + n * 8);
-    PTG_HIP(hipMemcpyAsync(ctx->tmp_a.p, xy, n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-    PTG_HIP(hipMemcpyAsync(ctx->tmp_b.p, sample_index, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(cfg), uint32_t(n),
                        ctx->tmp_a.as<uint2>(), ctx->tmp_b.as<int32_t>(), d_rays, d_sub);
     PTG_HIP(hipGetLastError());
@@ -2237,15 +2187,11 @@ int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t
 {
     if(int r = bind(ctx)) return r;
     if(int r = check_cfg(ctx, cfg, sample_end)) return r;
-    if(uint64_t(x0) + w > cfg->width || uint64_t(y0) + h > cfg->height) return fail(PTG_E_RANGE, "rectangle outside the image");
-    if(uint64_t(w) * h == 0) return PTG_OK;
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
+    if(pm.npix == 0) return PTG_OK;
     if(!out_albedo || !out_normal_depth) return fail(PTG_E_INVALID, "ptg_render_features: null output");
     if(sample_end <= sample_begin) return fail(PTG_E_INVALID, "empty sample range");
-    PixelMap pm{};
-    pm.tiles = 0;
-    pm.x0 = x0; pm.y0 = y0; pm.w = w; pm.h = h;
-    pm.img_w = cfg->width; pm.img_h = cfg->height;
-    pm.npix = w * h;
     // persistent blocks, each taking groups of kBlock / 8 pixels (4 waves of 8
     // pixels x 8 samples); every walk lane owns stack_bound entries of spill
     const uint32_t grid = std::min<uint32_t>(grid_for(pm.npix, kBlock / 8), std::max(1u, ctx->persistent_blocks / 4u));   // 8 per CU
@@ -2346,20 +2292,41 @@ int ptg_timing_enable(ptg_context* ctx, int enable)
     return PTG_OK;
 }
 
+// a recorded launch's device interval: start and end on one time axis
+// (relative to the first recorded start), and its length as the events give it
+struct Interval { int kind; double s, e, ms; };
+
+// The intervals of the launches recorded since timing was enabled or last
+// read, in recording order; waits for them and clears the record.
+static int take_intervals(ptg_context* ctx, std::vector<Interval>& iv)
+{
+    iv.clear();
+    iv.reserve(ctx->ev_used);
+    for(size_t i = 0; i < ctx->ev_used; ++i)
+    {
+        PTG_HIP(hipEventSynchronize(ctx->ev_stop[i]));
+        float s = 0, e = 0, t = 0;
+        PTG_HIP(hipEventElapsedTime(&s, ctx->ev_start[0], ctx->ev_start[i]));
+        PTG_HIP(hipEventElapsedTime(&e, ctx->ev_start[0], ctx->ev_stop[i]));
+        PTG_HIP(hipEventElapsedTime(&t, ctx->ev_start[i], ctx->ev_stop[i]));
+        iv.push_back(Interval{ctx->ev_kind[i], double(s), double(e), double(t)});
+    }
+    ctx->ev_used = 0;
+    return PTG_OK;
+}
+
 int ptg_last_kernel_times(ptg_context* ctx, double ms[8], uint32_t launches[8])
 {
     if(int r = bind(ctx)) return r;
     if(!ms || !launches) return fail(PTG_E_INVALID, "ptg_last_kernel_times: bad arguments");
+    std::vector<Interval> iv;
+    if(int r = take_intervals(ctx, iv)) return r;
     for(int k = 0; k < 8; ++k) { ms[k] = 0; launches[k] = 0; }
-    for(size_t i = 0; i < ctx->ev_used; ++i)
+    for(const Interval& v: iv)
     {
-        PTG_HIP(hipEventSynchronize(ctx->ev_stop[i]));
-        float t = 0;
-        PTG_HIP(hipEventElapsedTime(&t, ctx->ev_start[i], ctx->ev_stop[i]));
-        ms[ctx->ev_kind[i]] += t;
-        launches[ctx->ev_kind[i]] += 1;
+        ms[v.kind] += v.ms;
+        launches[v.kind] += 1;
     }
-    ctx->ev_used = 0;
     return PTG_OK;
 }
 
@@ -2367,26 +2334,16 @@ int ptg_last_kernel_busy(ptg_context* ctx, double busy_ms[8], double ms[8], uint
 {
     if(int r = bind(ctx)) return r;
     if(!busy_ms || !ms || !launches) return fail(PTG_E_INVALID, "ptg_last_kernel_busy: bad arguments");
-    struct Iv { int kind; double s, e; };
-    std::vector<Iv> iv;
-    iv.reserve(ctx->ev_used);
-    for(size_t i = 0; i < ctx->ev_used; ++i)
-    {
-        PTG_HIP(hipEventSynchronize(ctx->ev_stop[i]));
-        float s = 0, e = 0;
-        // every launch's interval on one time axis: relative to the first recorded start
-        PTG_HIP(hipEventElapsedTime(&s, ctx->ev_start[0], ctx->ev_start[i]));
-        PTG_HIP(hipEventElapsedTime(&e, ctx->ev_start[0], ctx->ev_stop[i]));
-        iv.push_back(Iv{ctx->ev_kind[i], double(s), double(e)});
-    }
-    std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& b) { return a.s < b.s; });
+    std::vector<Interval> iv;
+    if(int r = take_intervals(ctx, iv)) return r;
+    std::sort(iv.begin(), iv.end(), [](const Interval& a, const Interval& b) { return a.s < b.s; });
     for(int k = 0; k < 8; ++k)
     {
         busy_ms[k] = ms[k] = 0;
         launches[k] = 0;
         bool open = false;        // a merged interval [cs, ce] of kind k is open
         double cs = 0, ce = 0;
-        for(const Iv& v: iv)
+        for(const Interval& v: iv)
         {
             if(v.kind != k) continue;
             ms[k] += v.e - v.s;
@@ -2402,7 +2359,6 @@ int ptg_last_kernel_busy(ptg_context* ctx, double busy_ms[8], double ms[8], uint
         }
         if(open) busy_ms[k] += ce - cs;
     }
-    ctx->ev_used = 0;
     return PTG_OK;
 }
 

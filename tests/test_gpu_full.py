@@ -4,7 +4,8 @@ The oracle cannot render a whole 236-Msample frame in test time, so at full
 size the checks are:
   * spot rectangles of the full frame vs the oracle, bit for bit - chosen at
     the image corners, the centre and across the wavefront pipeline's chunk
-    boundaries (render_map splits a frame into chunks of ~2^24 paths);
+    boundaries (plan_chunks cuts a frame's samples into equal chunks of at
+    most 2^27 paths, two or more when both chunk pipelines run);
   * determinism: a second render gives the same bits;
   * the reference's own acceptance test (validator.py): PSNR of the 2x
     downscaled frame 0 against its committed output/frame_0000.bmp;

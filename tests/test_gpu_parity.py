@@ -110,6 +110,50 @@ def test_pipelines_identical(gpu, assets_dir):
     assert np.array_equal(_bits(outs[0][1]), _bits(outs[1][1]))
 
 
+def test_counting_and_timing_change_no_bits(gpu, assets_dir):
+    """A counting render (the kernels' COUNT instantiations) and a timed one
+    (events around every launch) give the bits of a plain render, in both
+    pipelines (the shape of test_pipelines_identical), and the timed render
+    records the launches the plan calls for: five bounce rounds; the
+    wavefront pipeline cuts the 24 samples into two chunks (16 + 8, one per
+    chunk pipeline), the megakernel renders them as one."""
+    W, H, SPP = 640, 360, 32
+    s = scene_for(assets_dir, W, H, SPP, frame=450)
+    gpu.upload_arrays(arrays_copy(s))
+    launches = {
+        "wavefront": {"megakernel": 0, "extend": 10, "shadow": 8, "shade": 10, "camera": 2, "accumulate": 2, "sky": 10,
+                      "classify": 10},
+        "megakernel": {"megakernel": 1, "extend": 0, "shadow": 0, "shade": 0, "camera": 0, "accumulate": 1, "sky": 0,
+                       "classify": 0},
+    }
+
+    def render():
+        bgra, acc = gpu.render(s.cfg, rect=(300, 150, 64, 36), samples=(0, 24), want_accum=True)
+        gpu.synchronize()
+        return bgra.cpu().numpy(), _bits(acc.cpu().numpy())
+
+    try:
+        for p in ("wavefront", "megakernel"):
+            gpu.set_pipeline(p)
+            plain = render()
+            gpu.enable_counters(True)
+            counted = render()
+            gpu.enable_counters(False)
+            gpu.enable_timing(True)
+            timed = render()
+            got = {k: n for k, (_, n) in gpu.kernel_times().items()}
+            gpu.enable_timing(False)
+            print(p, got)
+            for other in (counted, timed):
+                assert np.array_equal(plain[0], other[0]), p
+                assert np.array_equal(plain[1], other[1]), p
+            assert got == launches[p], p
+    finally:
+        gpu.set_pipeline("wavefront")
+        gpu.enable_counters(False)
+        gpu.enable_timing(False)
+
+
 def test_concurrency_levels_identical(gpu, assets_dir):
     """One stream, two streams, and two sample chunks in flight (the default)
     give the same bits; at 64 spp the frame is cut into two chunks, which the
