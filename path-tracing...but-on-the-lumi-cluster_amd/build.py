@@ -68,8 +68,10 @@ def build_test_kernels(verbose=False):
 
 def build_tools(verbose=False):
     """tools/_bin/walk_sim: the CPU model of the block walk over the upload's own
-    packing (tests/test_block_bvh.py)."""
+    packing (tests/test_block_bvh.py), and tests/frame_records/_bin/records_test,
+    the CPU test of the upload's per-frame records (tests/test_frame_records.py)."""
     _run(["make", "walk_sim"], os.path.join(ROOT, "tools"), verbose)
+    _run(["make"], os.path.join(ROOT, "tests", "frame_records"), verbose)
 
 
 def prepare_assets():

@@ -363,12 +363,47 @@ static void dedup_tlas(FramePack& fp)
     fp.tlas.swap(out);
 }
 
-int BlockCache::pack_frame(const ptg_bvh_node* static_nodes, const ptg_bvh_link* static_links, size_t static_count,
-                           size_t index_count, size_t vertex_count, const ptg_subframe* subframes, size_t subframe_count,
-                           const ptg_tlas_instance* instances, size_t instance_count, const ptg_bvh_node* frame_nodes,
-                           const ptg_bvh_link* frame_links, size_t first_node, size_t frame_node_count, FramePack& fp,
-                           std::string& err) const
+void BlockCache::clear()
 {
+    nodes.clear();
+    links.clear();
+    indices.clear();
+    pos.clear();
+    attrs_finite = false;
+    leaf_bounds_ok.clear();
+    blas.clear();
+    records.clear();
+    blas_stack = 0;
+    packed_mesh.clear();
+}
+
+void BlockCache::set_scene(const ptg_bvh_node* scene_nodes, const ptg_bvh_link* scene_links, size_t node_count,
+                           const uint32_t* scene_indices, size_t index_count, const ptg_float3* scene_pos,
+                           const ptg_float4* albedo, const ptg_float4* material, size_t vertex_count)
+{
+    clear();
+    // the BLASes are packed into blocks on the host when an instance first names them
+    nodes.assign(scene_nodes, scene_nodes + node_count);
+    links.assign(scene_links, scene_links + 8 * node_count);
+    indices.assign(scene_indices, scene_indices + index_count);
+    pos.assign(scene_pos, scene_pos + vertex_count);
+    // whether every vertex albedo and material value is finite: the surface
+    // pass retires a zero-throughput path at its last bounce only then
+    // (last_bounce_moot: the term it skips is att * X with X made of them)
+    attrs_finite = true;
+    for(size_t i = 0; i < vertex_count && attrs_finite; ++i)
+        attrs_finite = std::isfinite(albedo[i].x) && std::isfinite(albedo[i].y) && std::isfinite(albedo[i].z) &&
+                       std::isfinite(albedo[i].w) && std::isfinite(material[i].x) && std::isfinite(material[i].y) &&
+                       std::isfinite(material[i].z) && std::isfinite(material[i].w);
+}
+
+int BlockCache::pack_frame(const ptg_subframe* subframes, size_t subframe_count, const ptg_tlas_instance* instances,
+                           size_t instance_count, const ptg_bvh_node* frame_nodes, const ptg_bvh_link* frame_links,
+                           size_t first_node, size_t frame_node_count, FramePack& fp, std::string& err) const
+{
+    const ptg_bvh_node* static_nodes = nodes.data();
+    const ptg_bvh_link* static_links = links.data();
+    const size_t static_count = nodes.size(), index_count = indices.size(), vertex_count = pos.size();
     fp = FramePack();
     fp.blas_base = uint32_t(blas.size() / kBlockCopies);
     fp.blas_stack = blas_stack;
@@ -475,14 +510,105 @@ int BlockCache::pack_frame(const ptg_bvh_node* static_nodes, const ptg_bvh_link*
         if(r >= total) { err = "TLAS root outside the block buffer"; return PTG_E_RANGE; }
     for(uint32_t r: fp.inst_root)
         if(r >= total) { err = "BLAS root outside the block buffer"; return PTG_E_RANGE; }
+
+    fp.inst_trav.resize(instance_count);
+    fp.inst_shade.resize(instance_count);
+    for(size_t i = 0; i < instance_count; ++i)
+    {
+        const ptg_tlas_instance& in = instances[i];
+        const uint32_t handle[4] = {fp.inst_root[i], in.m.index_offset / 3, 0u, 0u};
+        for(int k = 0; k < 4; ++k)
+        {
+            float* row = fp.inst_trav[i].row[k];
+            row[0] = in.inv_transform.r[k].x;
+            row[1] = in.inv_transform.r[k].y;
+            row[2] = in.inv_transform.r[k].z;
+            memcpy(&row[3], &handle[k], 4);
+        }
+        InstShade& is = fp.inst_shade[i];
+        for(int k = 0; k < 3; ++k)
+        {
+            is.rot[k * 3 + 0] = in.transform.r[k].x;
+            is.rot[k * 3 + 1] = in.transform.r[k].y;
+            is.rot[k * 3 + 2] = in.transform.r[k].z;
+        }
+        is.index_offset = in.m.index_offset;
+        is.base_vertex_offset = in.m.base_vertex_offset;
+        std::fill(is.pad, is.pad + 5, 0u);
+        if(!packed_mesh.count(in.m.index_offset) && fp.new_mesh.insert(in.m.index_offset).second)
+            fp.mesh_jobs.push_back(MeshJob{in.m.index_offset, in.m.triangle_count, in.m.base_vertex_offset, 0});
+    }
+
+    // Per instance its TLAS leaf box and the subframes whose TLAS holds it
+    // (InstBox, the any-hit walk's occluder candidates): read from the
+    // reference-layout TLAS nodes (octant 0's links name the leaves).  A static
+    // instance is a leaf of every subframe's TLAS with the same box (computed
+    // from its transform alone, bvh.cc:259-281); a dynamic one of exactly one.
+    // Anything else is never a candidate.
+    // A candidate triangle's BLAS leaf box is computed from its vertices: the
+    // instance offers triangle candidates (tri_count > 0) only if every leaf
+    // box of its BLAS is exactly its triangle's bounds (checked once per pair).
+    auto bounds_ok = [&](const ptg_tlas_instance& in) {
+        const auto key = std::make_tuple(in.blas.node_offset, in.m.index_offset, in.m.base_vertex_offset);
+        auto it = leaf_bounds_ok.find(key);
+        if(it != leaf_bounds_ok.end()) return it->second;
+        const bool ok = leaf_boxes_are_vertex_bounds(
+            static_nodes + in.blas.node_offset, static_links + size_t(in.blas.node_offset) * 8, in.blas.node_count,
+            indices.data(), indices.size(), pos.data(), pos.size(), in.m.index_offset, in.m.triangle_count,
+            in.m.base_vertex_offset);
+        leaf_bounds_ok[key] = ok;
+        return ok;
+    };
+    std::vector<InstBox>& ib = fp.inst_box;
+    ib.resize(instance_count);
+    {
+        // seen: the distinct subframes whose TLAS names the instance; an
+        // instance named twice by one TLAS is never a candidate (the
+        // reference builder makes no such frame, the public upload could)
+        std::vector<uint32_t> seen(instance_count, 0), last_sf(instance_count, 0xFFFFFFFFu);
+        for(size_t i = 0; i < instance_count; ++i)
+        {
+            const uint32_t tris = bounds_ok(instances[i]) ? instances[i].m.triangle_count : 0u;
+            ib[i] = InstBox{{0, 0, 0}, kInstNoCandidate, {0, 0, 0}, tris};
+        }
+        for(size_t sf = 0; sf < subframe_count; ++sf)
+        {
+            const ptg_bvh tl = subframes[sf].tlas;   // ranges validated above
+            const size_t base = size_t(tl.node_offset) - first_node;
+            for(uint32_t n = 0; n < tl.node_count; ++n)
+            {
+                const ptg_bvh_link& l = frame_links[8 * base + n];
+                if(!(l.accept & 0x80000000u)) continue;
+                const uint32_t i = l.accept & 0x7FFFFFFFu;
+                if(i >= instance_count) continue;
+                const ptg_bvh_node& nd = frame_nodes[base + n];
+                const InstBox b{{nd.min_x, nd.min_y, nd.min_z}, uint32_t(sf), {nd.max_x, nd.max_y, nd.max_z}, ib[i].tri_count};
+                if(last_sf[i] == uint32_t(sf))
+                {   // twice in this subframe's TLAS
+                    ib[i].sub = kInstNoCandidate;
+                    seen[i] = 0xFFFFFFFFu;
+                    continue;
+                }
+                last_sf[i] = uint32_t(sf);
+                if(seen[i] == 0xFFFFFFFFu) continue;
+                if(seen[i]++ == 0) ib[i] = b;
+                else if(memcmp(ib[i].lo, b.lo, 12) != 0 || memcmp(ib[i].hi, b.hi, 12) != 0) ib[i].sub = kInstNoCandidate;
+            }
+        }
+        for(size_t i = 0; i < instance_count; ++i)
+            if(seen[i] == 0xFFFFFFFFu) ib[i].sub = kInstNoCandidate;
+            else if(seen[i] > 1 && ib[i].sub != kInstNoCandidate)
+                ib[i].sub = seen[i] == subframe_count ? kInstAllSubframes : kInstNoCandidate;
+    }
     return PTG_OK;
 }
 
-void BlockCache::commit(FramePack& fp)
+void BlockCache::commit(const FramePack& fp)
 {
     blas.insert(blas.end(), fp.new_blas.begin(), fp.new_blas.end());
     for(const auto& kv: fp.new_records) records[kv.first] = kv.second;
     blas_stack = fp.blas_stack;
+    packed_mesh.insert(fp.new_mesh.begin(), fp.new_mesh.end());
 }
 
 } // namespace ptg

@@ -1,8 +1,14 @@
-// Host packer of the block BVH records (device/block_format.h).
+// Host packer of the block BVH records (device/block_format.h) and of the
+// per-instance records (device/records.h): the host half of the uploads.
 #pragma once
 #include "ptg.h"
 #include "../device/block_format.h"
+#include "../device/records.h"
+#include <map>
 #include <string>
+#include <tuple>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 namespace ptg {
@@ -28,12 +34,6 @@ struct BlockBvh {
 bool pack_block_bvh(const ptg_bvh_node* nodes, const ptg_bvh_link* links, uint32_t count, uint32_t block_base,
                     uint32_t payload_limit, std::vector<BlockCopy>& out, BlockBvh& info, std::string& err);
 
-} // namespace ptg
-
-#include <unordered_map>
-
-namespace ptg {
-
 // Whether every leaf box of a BLAS (nodes[0..count), links in the reference
 // layout) is exactly the bounds of its triangle's three positions as the
 // reference's builder computes them (bvh.cc:243-246: fmin / fmax, the float
@@ -55,7 +55,9 @@ struct BlasRecord {
     uint32_t max_payload = 0;   // largest triangle index its leaves name
 };
 
-// What one frame upload adds to the block buffer [BLAS blocks][TLAS blocks].
+// What one frame upload writes: the blocks it adds to the block buffer
+// [BLAS blocks][TLAS blocks], the per-instance records, and the meshes whose
+// triangle records the device still has to pack.
 struct FramePack {
     uint32_t blas_base = 0;                 // block index of new_blas[0]
     uint32_t tlas_base = 0;                 // block index of tlas[0]
@@ -65,37 +67,61 @@ struct FramePack {
     std::vector<uint32_t> tlas_root;        // per subframe
     std::vector<uint32_t> inst_root;        // per instance: its BLAS's root block
     uint32_t blas_stack = 0, tlas_stack = 0;
+    std::vector<InstTrav> inst_trav;       // per instance (device/records.h)
+    std::vector<InstShade> inst_shade;
+    std::vector<InstBox> inst_box;
+    std::vector<MeshJob> mesh_jobs;        // meshes no committed frame packed, by first appearance
+    std::unordered_set<uint32_t> new_mesh; // their index_offsets
     uint32_t total_blocks() const { return tlas_base + uint32_t(tlas.size() / kBlockCopies); }
     uint32_t stack_bound() const { return blas_stack + tlas_stack; }   // stack entries a walk can hold
 };
 
-// The BLAS blocks packed so far and the packing of a frame's handles: the
-// host half of ptg_upload_frame, kept free of device code so the CPU tests
-// (tools/walk_sim.cpp) run exactly what the upload runs.
+// The host half of ptg_upload_scene and ptg_upload_frame, kept free of device
+// code so the CPU tests (tools/walk_sim.cpp, tests/frame_records) run exactly
+// what the uploads run: a host copy of the static scene, the BLAS blocks
+// packed so far, and the packing of a frame's handles into blocks and
+// per-instance records.
 struct BlockCache {
+    // the static scene (set_scene): the BLAS nodes + links in reference layout
+    // (packed into blocks when an instance first names a BLAS) and the mesh
+    // arrays the occluder candidates' leaf boxes are checked against
+    std::vector<ptg_bvh_node> nodes;
+    std::vector<ptg_bvh_link> links;
+    std::vector<uint32_t> indices;
+    std::vector<ptg_float3> pos;
+    bool attrs_finite = false;                            // every vertex albedo / material value finite
+    // per (BLAS, mesh): every BLAS leaf's box is its triangle's vertex bounds
+    // (bvh.cc:243-246), so a candidate triangle's leaf box can be computed from
+    // its vertices (k_wf_walk<ANY>); checked once per pair (a memo of a pure
+    // function of the scene: pack_frame fills it)
+    mutable std::map<std::tuple<uint32_t, uint32_t, uint32_t>, bool> leaf_bounds_ok;
     std::vector<BlockCopy> blas;                         // committed BLAS blocks
     std::unordered_map<uint32_t, BlasRecord> records;     // BLAS node_offset -> record
     uint32_t blas_stack = 0;                              // largest committed BLAS stack bound
+    std::unordered_set<uint32_t> packed_mesh;             // index_offsets of the meshes whose triangle records are on the device
 
-    void clear()
-    {
-        blas.clear();
-        records.clear();
-        blas_stack = 0;
-    }
+    // Forgets the scene and everything packed from it.
+    void clear();
+    // Replaces the static scene: copies the arrays (may throw std::bad_alloc)
+    // and scans the vertex attributes for attrs_finite.  Nothing packed from
+    // the previous scene survives.
+    void set_scene(const ptg_bvh_node* scene_nodes, const ptg_bvh_link* scene_links, size_t node_count,
+                   const uint32_t* scene_indices, size_t index_count, const ptg_float3* scene_pos,
+                   const ptg_float4* albedo, const ptg_float4* material, size_t vertex_count);
     // Checks every handle of the frame (BLAS and mesh ranges, TLAS ranges,
-    // leaf payloads, block links) and packs the BLASes not yet cached plus
-    // every subframe's TLAS.  `static_nodes/links` are the scene's BLAS
-    // arrays (reference layout), `frame_nodes/links` the frame's TLAS arrays
+    // leaf payloads, block links), packs the BLASes not yet cached plus every
+    // subframe's TLAS, and fills the per-instance records and the mesh jobs.
+    // `frame_nodes/links` are the frame's TLAS arrays (reference layout)
     // starting at global node `first_node`.  Returns PTG_OK, or PTG_E_RANGE
-    // with the reason in `err`; the cache is not modified.
-    int pack_frame(const ptg_bvh_node* static_nodes, const ptg_bvh_link* static_links, size_t static_count,
-                   size_t index_count, size_t vertex_count, const ptg_subframe* subframes, size_t subframe_count,
-                   const ptg_tlas_instance* instances, size_t instance_count, const ptg_bvh_node* frame_nodes,
-                   const ptg_bvh_link* frame_links, size_t first_node, size_t frame_node_count, FramePack& fp,
-                   std::string& err) const;
-    // Adds a successfully uploaded frame's new BLASes to the cache.
-    void commit(FramePack& fp);
+    // with the reason in `err`; the cache is not modified (leaf_bounds_ok aside).
+    int pack_frame(const ptg_subframe* subframes, size_t subframe_count, const ptg_tlas_instance* instances,
+                   size_t instance_count, const ptg_bvh_node* frame_nodes, const ptg_bvh_link* frame_links,
+                   size_t first_node, size_t frame_node_count, FramePack& fp, std::string& err) const;
+    // What a frame packs joins the cache here and nowhere else, after every
+    // upload of it succeeded: its new BLASes, their records and stack bound,
+    // and its new meshes.  An upload that fails half-way never leaves the
+    // cache claiming records that were not written.
+    void commit(const FramePack& fp);
 };
 
 } // namespace ptg

@@ -24,14 +24,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <tuple>
 #include <string>
 #include <type_traits>
 #include <vector>
 #include <unordered_map>
-#include <unordered_set>
 #include "host/block_bvh.h"
 #include <vector>
 
@@ -69,10 +66,6 @@ __global__ void k_polygon_table(const uint8_t* __restrict__ subframes, uint32_t 
         v = polygon_vertex(rd_f(cam, 76), (uint32_t)sides, (float)k);
     out[t] = make_float2(v.x, v.y);
 }
-
-struct MeshJob {
-    uint32_t index_offset, triangle_count, base_vertex_offset, pad;
-};
 
 // one thread per triangle of each new mesh: its TriRec (positions) and its
 // TriShade (normals, albedos, materials), both at index_offset / 3 + t
@@ -1079,21 +1072,11 @@ struct ptg_context {
     int device = 0;
     hipStream_t stream = nullptr;
     bool counting = false;
-    // static scene: the shading arrays in reference layout, the triangle
-    // records, and a host copy of the BLAS nodes + links (packed into blocks
-    // when an instance first names a BLAS)
+    // static scene: the shading arrays in reference layout and the triangle
+    // records
     DevBuf indices, pos, normal, albedo, material, tris, tri_shade;
-    std::vector<ptg_bvh_node> host_nodes;
-    std::vector<ptg_bvh_link> host_links;
-    std::vector<uint32_t> host_indices;    // the mesh arrays the occluder candidates' leaf boxes are checked against
-    std::vector<ptg_float3> host_pos;
-    // per (BLAS, mesh): every BLAS leaf's box is its triangle's vertex bounds
-    // (bvh.cc:243-246), so a candidate triangle's leaf box can be computed from
-    // its vertices (k_wf_walk<ANY>); checked once per pair on the host
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, bool> leaf_bounds_ok;
-    size_t static_nodes = 0, index_count = 0, vertex_count = 0;
-    std::unordered_set<uint32_t> packed_mesh;
-    // BLAS blocks packed so far (host copy; their device copy leads `blocks`)
+    // the host's copy of the scene and everything packed from it so far
+    // (host/block_bvh.h; the BLAS blocks' device copy leads `blocks`)
     BlockCache cache;
     size_t blas_on_device = 0;                           // leading cache.blas entries already in `blocks`
     bool scene_ready = false;
@@ -1103,9 +1086,7 @@ struct ptg_context {
     uint32_t stage_next = 0;
     size_t block_count = 0, subframe_count = 0, instance_count = 0;
     uint32_t stack_bound = 0;                            // TLAS + BLAS stack bound of this frame (entries)
-    bool attrs_finite = false;                           // every vertex albedo / material value finite
     std::vector<uint32_t> host_tlas_root;
-    std::vector<ptg_subframe> host_subframes;
     bool frame_ready = false;
     // render workspace
     DevBuf acc, tmp_a, tmp_b, tmp_c, counters;
@@ -1212,10 +1193,10 @@ struct ptg_context {
         s.block_count = uint32_t(block_count);
         s.spill = nullptr;
         s.spill_stride = stack_bound;
-        s.tri_count = uint32_t(index_count / 3);
+        s.tri_count = uint32_t(cache.indices.size() / 3);
         s.inst_count = uint32_t(instance_count);
         s.debug = PTG_DEBUG ? debug.as<uint32_t>() : nullptr;
-        s.attrs_finite = attrs_finite ? 1u : 0u;
+        s.attrs_finite = cache.attrs_finite ? 1u : 0u;
         return s;
     }
 };
@@ -1725,16 +1706,10 @@ int ptg_upload_scene(ptg_context* ctx, const ptg_bvh_node* nodes, const ptg_bvh_
     if(node_count >= (1u << 28) / 8 || index_count >= (1u << 31) || vertex_count >= (1u << 31))
         return fail(PTG_E_RANGE, "ptg_upload_scene: scene too large for 32-bit indexing");
     ctx->scene_ready = ctx->frame_ready = false;
-    ctx->packed_mesh.clear();
-    ctx->cache.clear();
     ctx->blas_on_device = 0;
     try
-    {   // the BLASes are packed into blocks on the host when an instance first names them
-        ctx->host_nodes.assign(nodes, nodes + node_count);
-        ctx->host_links.assign(links, links + 8 * node_count);
-        ctx->host_indices.assign(indices, indices + index_count);
-        ctx->host_pos.assign(pos, pos + vertex_count);
-        ctx->leaf_bounds_ok.clear();
+    {
+        ctx->cache.set_scene(nodes, links, node_count, indices, index_count, pos, albedo, material, vertex_count);
     }
     catch(const std::bad_alloc&)
     {
@@ -1759,17 +1734,6 @@ int ptg_upload_scene(ptg_context* ctx, const ptg_bvh_node* nodes, const ptg_bvh_
     PTG_HIP(hipMemcpyAsync(ctx->albedo.p, albedo, vertex_count * 16, hipMemcpyHostToDevice, s));
     PTG_HIP(hipMemcpyAsync(ctx->material.p, material, vertex_count * 16, hipMemcpyHostToDevice, s));
     PTG_HIP(hipStreamSynchronize(s));
-    // whether every vertex albedo and material value is finite: the surface
-    // pass retires a zero-throughput path at its last bounce only then
-    // (last_bounce_moot: the term it skips is att * X with X made of them)
-    ctx->attrs_finite = true;
-    for(size_t i = 0; i < vertex_count && ctx->attrs_finite; ++i)
-        ctx->attrs_finite = std::isfinite(albedo[i].x) && std::isfinite(albedo[i].y) && std::isfinite(albedo[i].z) &&
-                            std::isfinite(albedo[i].w) && std::isfinite(material[i].x) && std::isfinite(material[i].y) &&
-                            std::isfinite(material[i].z) && std::isfinite(material[i].w);
-    ctx->static_nodes = node_count;
-    ctx->index_count = index_count;
-    ctx->vertex_count = vertex_count;
     ctx->scene_ready = true;
     return PTG_OK;
 }
@@ -1784,106 +1748,17 @@ int upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subfram
     ctx->frame_ready = false;
     hipStream_t s = ctx->stream;
 
-    // Validate every handle and pack the BLASes no earlier frame named plus
-    // this frame's TLASes (host/block_bvh.cpp, checked there before any
-    // kernel can follow a block link).  What this call packs joins the cache
-    // only after every upload succeeded: an upload that fails half-way never
-    // leaves the cache claiming records that were not written.
+    // Validate every handle, pack the BLASes no earlier frame named plus
+    // this frame's TLASes, and build the per-instance records and the mesh
+    // jobs (host/block_bvh.cpp, checked there before any kernel can follow a
+    // block link).  What this call packs joins the cache only at the commit
+    // below.
     FramePack fp;
     std::string err;
-    if(int r = ctx->cache.pack_frame(ctx->host_nodes.data(), ctx->host_links.data(), ctx->static_nodes, ctx->index_count,
-                                     ctx->vertex_count, subframes, subframe_count, instances, instance_count, frame_nodes,
-                                     frame_links, first_node, frame_node_count, fp, err))
+    if(int r = ctx->cache.pack_frame(subframes, subframe_count, instances, instance_count, frame_nodes, frame_links,
+                                     first_node, frame_node_count, fp, err))
         return fail(r, "ptg_upload_frame: " + err);
-    std::vector<InstTrav> it(instance_count);
-    std::vector<InstShade> is(instance_count);
-    std::vector<MeshJob> mesh_jobs;
-    std::unordered_set<uint32_t> new_mesh;
-    for(size_t i = 0; i < instance_count; ++i)
-    {
-        const ptg_tlas_instance& in = instances[i];
-        const uint32_t handle[4] = {fp.inst_root[i], in.m.index_offset / 3, 0u, 0u};
-        for(int k = 0; k < 4; ++k)
-        {
-            float w;
-            memcpy(&w, &handle[k], 4);
-            it[i].row[k] = make_float4(in.inv_transform.r[k].x, in.inv_transform.r[k].y, in.inv_transform.r[k].z, w);
-        }
-        for(int k = 0; k < 3; ++k)
-        {
-            is[i].rot[k * 3 + 0] = in.transform.r[k].x;
-            is[i].rot[k * 3 + 1] = in.transform.r[k].y;
-            is[i].rot[k * 3 + 2] = in.transform.r[k].z;
-        }
-        is[i].index_offset = in.m.index_offset;
-        is[i].base_vertex_offset = in.m.base_vertex_offset;
-        std::fill(is[i].pad, is[i].pad + 5, 0u);
-        if(!ctx->packed_mesh.count(in.m.index_offset) && new_mesh.insert(in.m.index_offset).second)
-            mesh_jobs.push_back(MeshJob{in.m.index_offset, in.m.triangle_count, in.m.base_vertex_offset, 0});
-    }
-
-    // Per instance its TLAS leaf box and the subframes whose TLAS holds it
-    // (InstBox, the any-hit walk's occluder candidates): read from the
-    // reference-layout TLAS nodes (octant 0's links name the leaves).  A static
-    // instance is a leaf of every subframe's TLAS with the same box (computed
-    // from its transform alone, bvh.cc:259-281); a dynamic one of exactly one.
-    // Anything else is never a candidate.
-    // A candidate triangle's BLAS leaf box is computed from its vertices: the
-    // instance offers triangle candidates (tri_count > 0) only if every leaf
-    // box of its BLAS is exactly its triangle's bounds (checked once per pair).
-    auto leaf_bounds_ok = [&](const ptg_tlas_instance& in) {
-        const auto key = std::make_tuple(in.blas.node_offset, in.m.index_offset, in.m.base_vertex_offset);
-        auto it = ctx->leaf_bounds_ok.find(key);
-        if(it != ctx->leaf_bounds_ok.end()) return it->second;
-        // (host code built by the host compiler with the builder's flags:
-        // fmin / fmax with the reference's tie rule, host/block_bvh.cpp)
-        const bool ok = leaf_boxes_are_vertex_bounds(
-            ctx->host_nodes.data() + in.blas.node_offset, ctx->host_links.data() + size_t(in.blas.node_offset) * 8,
-            in.blas.node_count, ctx->host_indices.data(), ctx->host_indices.size(), ctx->host_pos.data(),
-            ctx->host_pos.size(), in.m.index_offset, in.m.triangle_count, in.m.base_vertex_offset);
-        ctx->leaf_bounds_ok[key] = ok;
-        return ok;
-    };
-    std::vector<InstBox> ib(instance_count);
-    {
-        // seen: the distinct subframes whose TLAS names the instance; an
-        // instance named twice by one TLAS is never a candidate (the
-        // reference builder makes no such frame, the public upload could)
-        std::vector<uint32_t> seen(instance_count, 0), last_sf(instance_count, 0xFFFFFFFFu);
-        for(size_t i = 0; i < instance_count; ++i)
-        {
-            const uint32_t tris = leaf_bounds_ok(instances[i]) ? instances[i].m.triangle_count : 0u;
-            ib[i] = InstBox{{0, 0, 0}, kInstNoCandidate, {0, 0, 0}, tris};
-        }
-        for(size_t sf = 0; sf < subframe_count; ++sf)
-        {
-            const ptg_bvh tl = subframes[sf].tlas;   // ranges validated by pack_frame
-            const size_t base = size_t(tl.node_offset) - first_node;
-            for(uint32_t n = 0; n < tl.node_count; ++n)
-            {
-                const ptg_bvh_link& l = frame_links[8 * base + n];
-                if(!(l.accept & 0x80000000u)) continue;
-                const uint32_t i = l.accept & 0x7FFFFFFFu;
-                if(i >= instance_count) continue;
-                const ptg_bvh_node& nd = frame_nodes[base + n];
-                const InstBox b{{nd.min_x, nd.min_y, nd.min_z}, uint32_t(sf), {nd.max_x, nd.max_y, nd.max_z}, ib[i].tri_count};
-                if(last_sf[i] == uint32_t(sf))
-                {   // twice in this subframe's TLAS
-                    ib[i].sub = kInstNoCandidate;
-                    seen[i] = 0xFFFFFFFFu;
-                    continue;
-                }
-                last_sf[i] = uint32_t(sf);
-                if(seen[i] == 0xFFFFFFFFu) continue;
-                if(seen[i]++ == 0) ib[i] = b;
-                else if(memcmp(ib[i].lo, b.lo, 12) != 0 || memcmp(ib[i].hi, b.hi, 12) != 0) ib[i].sub = kInstNoCandidate;
-            }
-        }
-        for(size_t i = 0; i < instance_count; ++i)
-            if(seen[i] == 0xFFFFFFFFu) ib[i].sub = kInstNoCandidate;
-            else if(seen[i] > 1 && ib[i].sub != kInstNoCandidate)
-                ib[i].sub = seen[i] == subframe_count ? kInstAllSubframes : kInstNoCandidate;
-    }
+    const std::vector<MeshJob>& mesh_jobs = fp.mesh_jobs;
 
     // Device copies, asynchronous: everything the frame uploads is gathered
     // into one of two pinned staging buffers and copied on the context's
@@ -1921,9 +1796,9 @@ int upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subfram
     parts.push_back({fp.new_blas.data(), fp.new_blas.size() * sizeof(BlockCopy), dev + old_blas.size()});
     parts.push_back({fp.tlas.data(), fp.tlas.size() * sizeof(BlockCopy), dev + blas_total});
     parts.push_back({fp.tlas_root.data(), subframe_count * sizeof(uint32_t), ctx->tlas_root.p});
-    parts.push_back({it.data(), instance_count * sizeof(InstTrav), ctx->inst_trav.p});
-    parts.push_back({is.data(), instance_count * sizeof(InstShade), ctx->inst_shade.p});
-    parts.push_back({ib.data(), instance_count * sizeof(InstBox), ctx->inst_box.p});
+    parts.push_back({fp.inst_trav.data(), instance_count * sizeof(InstTrav), ctx->inst_trav.p});
+    parts.push_back({fp.inst_shade.data(), instance_count * sizeof(InstShade), ctx->inst_shade.p});
+    parts.push_back({fp.inst_box.data(), instance_count * sizeof(InstBox), ctx->inst_box.p});
     parts.push_back({subframes, subframe_count * sizeof(ptg_subframe), ctx->subframes.p});
     parts.push_back({mesh_jobs.data(), mesh_jobs.size() * sizeof(MeshJob), ctx->jobs.p});
     size_t total = 0;
@@ -1955,16 +1830,14 @@ int upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subfram
         PTG_HIP(hipGetLastError());
     }
 
-    // commit
+    // every upload is queued: what this call packed joins the cache
     ctx->cache.commit(fp);
     ctx->blas_on_device = ctx->cache.blas.size();
-    ctx->packed_mesh.insert(new_mesh.begin(), new_mesh.end());
     ctx->block_count = fp.total_blocks();
     ctx->stack_bound = fp.stack_bound();
     ctx->host_tlas_root = fp.tlas_root;
     ctx->subframe_count = subframe_count;
     ctx->instance_count = instance_count;
-    ctx->host_subframes.assign(subframes, subframes + subframe_count);
     ctx->frame_ready = true;
     return PTG_OK;
 }
@@ -1979,7 +1852,7 @@ int ptg_upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t sub
     if(!ctx->scene_ready) return fail(PTG_E_INVALID, "ptg_upload_frame: upload the scene first");
     if(!subframes || !subframe_count || !instances || !instance_count || !frame_nodes || !frame_links || !frame_node_count)
         return fail(PTG_E_INVALID, "ptg_upload_frame: bad arguments");
-    if(first_node != ctx->static_nodes)
+    if(first_node != ctx->cache.nodes.size())
         return fail(PTG_E_INVALID, "ptg_upload_frame: first_node must equal the uploaded static node count");
     if(first_node + frame_node_count >= (1ull << 31)) return fail(PTG_E_RANGE, "ptg_upload_frame: too many nodes");
     try

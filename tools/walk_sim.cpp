@@ -542,13 +542,14 @@ int main(int argc, char** argv)
     // frame 0 first and committed, so that the frame under test also packs
     // BLASes at a nonzero block base, as a later frame upload does
     BlockCache cache;
+    cache.set_scene(v.nodes, v.links, v.static_node_count, v.indices, v.index_count, v.pos, v.albedo, v.material,
+                    v.vertex_count);
     FramePack fp;
     std::string err;
     auto pack = [&]() {
         ptg_scene_view w;
         ptg_scene_view_get(scene, &w);
-        return cache.pack_frame(w.nodes, w.links, w.static_node_count, w.index_count, w.vertex_count, w.subframes,
-                                w.subframe_count, w.instances, w.instance_count, w.nodes + w.static_node_count,
+        return cache.pack_frame(w.subframes, w.subframe_count, w.instances, w.instance_count, w.nodes + w.static_node_count,
                                 w.links + 8 * w.static_node_count, w.static_node_count, w.node_count - w.static_node_count, fp,
                                 err);
     };
@@ -600,17 +601,12 @@ int main(int argc, char** argv)
     }
     pk.inst_root = fp.inst_root;
     pk.tlas_root = fp.tlas_root;
-    {   // the any-hit candidates' requirement (the upload checks it per BLAS and mesh)
+    {   // the any-hit candidates' requirement (pack_frame checks it per BLAS and mesh:
+        // an instance that fails it offers no candidate triangles)
         ptg_scene_view w;
         ptg_scene_view_get(scene, &w);
         size_t bad = 0;
-        for(size_t i = 0; i < w.instance_count; ++i)
-        {
-            const ptg_tlas_instance& in = w.instances[i];
-            bad += leaf_boxes_are_vertex_bounds(w.nodes + in.blas.node_offset, w.links + size_t(in.blas.node_offset) * 8,
-                                                in.blas.node_count, w.indices, w.index_count, w.pos, w.vertex_count,
-                                                in.m.index_offset, in.m.triangle_count, in.m.base_vertex_offset) ? 0 : 1;
-        }
+        for(size_t i = 0; i < w.instance_count; ++i) bad += fp.inst_box[i].tri_count != 0 ? 0 : 1;
         printf("instances whose BLAS leaf boxes are not their vertex bounds: %zu of %zu\n", bad, w.instance_count);
         {   // and the check rejects a box that is not: instance 0's BLAS with one leaf box's
             // min_x lowered by one ulp, and with +0 / -0 swapped in a zero bound if it has one
@@ -1032,9 +1028,10 @@ int main(int argc, char** argv)
             diff += memcmp(&v.instances[i].m, &vB.instances[i].m, sizeof(ptg_mesh)) ||
                     memcmp(&v.instances[i].transform, &vB.instances[i].transform, 2 * sizeof(v.instances[i].transform));
         BlockCache cB;
+        cB.set_scene(vB.nodes, vB.links, vB.static_node_count, vB.indices, vB.index_count, vB.pos, vB.albedo, vB.material,
+                     vB.vertex_count);
         FramePack fB;
-        if(cB.pack_frame(vB.nodes, vB.links, vB.static_node_count, vB.index_count, vB.vertex_count, vB.subframes,
-                         vB.subframe_count, vB.instances, vB.instance_count, vB.nodes + vB.static_node_count,
+        if(cB.pack_frame(vB.subframes, vB.subframe_count, vB.instances, vB.instance_count, vB.nodes + vB.static_node_count,
                          vB.links + 8 * vB.static_node_count, vB.static_node_count, vB.node_count - vB.static_node_count, fB, err))
         { fprintf(stderr, "ANYHIER pack: %s\n", err.c_str()); return 1; }
         pkB.E = fB.new_blas;
