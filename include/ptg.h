@@ -305,6 +305,56 @@ int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_para
                 const ptg_float4* normal_depth,
                 ptg_float4* out_radiance, ptg_uchar4* out_bgra);
 
+/* ---- per-pixel sample moments and the variance-guided denoiser ----------
+ * ptg_render with one more output: how noisy each pixel's samples were.
+ * Rectangle, sample range, out_accum and out_bgra are ptg_render's, bit for
+ * bit.  out_moments (required, DEVICE pointer, [h][w] ptg_float4) gets, per
+ * pixel, over the samples j of [sample_begin, sample_end) in index order:
+ *   L_j = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z of c = path_trace_pixel(xy, j),
+ *   for the n samples whose three channels are finite (a non-finite sample
+ *   stays in the radiance sum and is left out here);
+ *   s1 = sum L_j, s2 = sum L_j*L_j, both float32 from +0 in index order;
+ *   m1 = s1/n, m2 = s2/n, var = max(m2 - m1*m1, 0) (0 for a NaN),
+ *   vm = var/(n - 1), the variance of the pixel's mean (0 when n < 2);
+ *   out_moments = (m1, m2, vm, (float)n), all 0 when n == 0.
+ * The moments are normalised by the n finite samples of the range rendered,
+ * NOT by cfg->samples_per_pixel as out_accum is: a partial sample range gives
+ * the moments of that range.  Every operation is one float32 rounding.  A
+ * null out_moments is PTG_E_INVALID.  Asynchronous on the context's stream. */
+int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg,
+                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                       uint32_t sample_begin, uint32_t sample_end,
+                       ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments);
+
+/* ptg_denoise with the luminance range set per pixel by the variance of the
+ * pixel's mean (moments.z of ptg_render_moments) instead of a fixed
+ * sigma_color: each pass prefilters the variance over 3 x 3 pixels, weighs a
+ * tap's luminance difference by sigma_luminance * sqrt(variance) +
+ * variance_floor, and filters the variance along with the image (weights
+ * squared), so later passes narrow by themselves.  The guide terms are
+ * ptg_denoise's.  Defined to the bit in DESIGN.md;
+ * denoise.atrous_guided_reference is the CPU restatement. */
+typedef struct {
+    uint32_t iterations;   /* 0..8 passes; pass k has taps 2^k pixels apart */
+    float sigma_luminance; /* luminance distance scale, in standard deviations of the pixel's mean */
+    float sigma_albedo;    /* albedo + coverage distance scale */
+    float sigma_normal;    /* normal distance scale */
+    float sigma_depth;     /* relative depth distance scale */
+    float albedo_floor;    /* radiance is divided by max(albedo, albedo_floor) before filtering */
+    float variance_floor;  /* added to the luminance scale, so a noiseless pixel still has a range */
+} ptg_denoise_guided_params;
+void ptg_denoise_guided_params_default(ptg_denoise_guided_params* params);
+/* radiance, albedo, normal_depth, out_radiance, out_bgra as for ptg_denoise;
+ * moments: [h][w] ptg_float4 as written by ptg_render_moments (only .z is
+ * read; a negative or non-finite .z counts as 0).  iterations > 8, or a float
+ * field that is not positive and finite, is PTG_E_INVALID; iterations == 0
+ * copies the radiance bits unchanged.  DEVICE pointers; asynchronous on the
+ * context's stream. */
+int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_guided_params* params,
+                       const ptg_float4* radiance, const ptg_float4* albedo,
+                       const ptg_float4* normal_depth, const ptg_float4* moments,
+                       ptg_float4* out_radiance, ptg_uchar4* out_bgra);
+
 /* Work counters of the last ptg_render* call (filled only while counting is
  * on, ptg_counters_enable; counting uses a separate, slower build of the
  * kernels):

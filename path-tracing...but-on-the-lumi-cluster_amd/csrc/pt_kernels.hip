@@ -7,6 +7,7 @@
 //                   [sample][pixel] float4 buffer in HBM
 //   k_accumulate    baseline_render's j-ordered float32 sum over the chunk,
 //                   then (last chunk) / SPP + tonemap_pixel (main.cc:24-43)
+//   k_accumulate_moments  the same fold, keeping the samples' luminance moments too
 //   k_sample_list   path_trace_pixel for an explicit (x, y, j) list (parity)
 //   k_rays          ray_query closest hit + shadow any-hit (parity)
 //   k_tonemap, k_scatter_tiles
@@ -765,6 +766,71 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
     if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
 }
 
+// Rec. 709 luminance of the moments and of the guided denoiser: three
+// products, two sums, each one float32 rounding
+__device__ __forceinline__ float lum709(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
+// k_accumulate with, in the same pass over the chunk, the first two
+// luminance moments of its finite samples (ptg_render_moments).  The radiance
+// sum is k_accumulate's operation for operation.  mom[p] = (s1, s2, n as
+// bits, -) carries across chunks as acc does; on the last chunk
+// out_moments[p] = (m1, m2, variance of the mean, n), normalised by n.
+__global__ __launch_bounds__(kBlock) void k_accumulate_moments(PixelMap pm, uint32_t nj, const float4* __restrict__ samples,
+                                                               float4* __restrict__ acc, float4* __restrict__ mom, int first,
+                                                               int last, float spp, float4* __restrict__ out_accum,
+                                                               uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= pm.npix) return;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    float s1 = 0.0f, s2 = 0.0f;
+    uint32_t n = 0;
+    if(!first)
+    {
+        const float4 a = acc[p];
+        ax = a.x; ay = a.y; az = a.z;
+        const float4 m = mom[p];
+        s1 = m.x; s2 = m.y; n = __float_as_uint(m.z);
+    }
+    for(uint32_t j = 0; j < nj; ++j)
+    {
+        const float4 s = ld_out(samples + size_t(j) * pm.npix + p);
+        ax = ax + s.x;
+        ay = ay + s.y;
+        az = az + s.z;
+        if(finite3(V3(s.x, s.y, s.z)))
+        {
+            const float L = lum709(s.x, s.y, s.z);
+            s1 = s1 + L;
+            s2 = s2 + L * L;
+            ++n;
+        }
+    }
+    if(!last)
+    {
+        acc[p] = make_float4(ax, ay, az, 0.f);
+        mom[p] = make_float4(s1, s2, __uint_as_float(n), 0.f);
+        return;
+    }
+    ax = ax / spp;
+    ay = ay / spp;
+    az = az / spp;
+    uint32_t x, y;
+    const bool inside = pm.pixel(p, x, y);
+    if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if(inside && n > 0)
+    {
+        const float nf = (float)n;
+        const float m1 = s1 / nf, m2 = s2 / nf;
+        const float d = m2 - m1 * m1;
+        const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
+        r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
+    }
+    out_moments[p] = r;
+}
+
 __global__ __launch_bounds__(kBlock) void k_sample_list(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
                                                         const int32_t* __restrict__ js, float4* __restrict__ out)
 {
@@ -999,6 +1065,104 @@ __global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, 
     if(out_bgra) out_bgra[i] = tonemap(c);
 }
 
+// a variance the guided denoiser may use: >= 0 and finite, else 0
+__device__ __forceinline__ float dn_var_ok(float v) { return (v >= 0.0f && __builtin_isfinite(v)) ? v : 0.0f; }
+
+// ptg_denoise_guided's image: (I0, V0) = (radiance / max(albedo, floor), the
+// variance of the pixel's mean luminance (moments.z) / lum(max(albedo, floor))^2)
+__global__ __launch_bounds__(kBlock) void k_dn_demodulate_guided(uint32_t n, float fl, const float4* __restrict__ radiance,
+                                                                 const float4* __restrict__ albedo,
+                                                                 const float4* __restrict__ moments, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) return;
+    const float4 r = radiance[i], a = albedo[i];
+    const float mx = dn_floor(a.x, fl), my = dn_floor(a.y, fl), mz = dn_floor(a.z, fl);
+    const float v = dn_var_ok(moments[i].z);
+    const float ml = lum709(mx, my, mz);
+    out[i] = make_float4(r.x / mx, r.y / my, r.z / mz, dn_var_ok(v / (ml * ml)));
+}
+
+struct DenoiseGuidedStep {
+    uint32_t w, h, step;
+    float sigma_luminance, variance_floor;
+    float var_albedo, var_normal, var_depth;              // sigma * sigma
+};
+
+// One variance-guided a-trous iteration over (I.xyz, V), one work-item per
+// pixel: a 3 x 3 prefilter of V at distance 1 sets the luminance range, then
+// k_dn_atrous's 5 x 5 taps `step` apart filter I with the weights and V with
+// their squares.  Every operation is one float32 rounding in DESIGN.md's order.
+__global__ __launch_bounds__(kBlock) void k_dn_atrous_guided(DenoiseGuidedStep a, const float4* __restrict__ I,
+                                                             const float4* __restrict__ albedo,
+                                                             const float4* __restrict__ normal_depth,
+                                                             float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= a.w * a.h) return;
+    const int32_t x = (int32_t)(i % a.w), y = (int32_t)(i / a.w);
+    const float4 Ip = I[i], Ap = albedo[i], Np = normal_depth[i];
+    float gs = 0.0f, gn = 0.0f;
+    for(int32_t dy = -1; dy <= 1; ++dy)
+    {
+        const int32_t qy = y + dy;
+        if(qy < 0 || qy >= (int32_t)a.h) continue;
+        const float ty = dy == 0 ? 0.5f : 0.25f;
+        for(int32_t dx = -1; dx <= 1; ++dx)
+        {
+            const int32_t qx = x + dx;
+            if(qx < 0 || qx >= (int32_t)a.w) continue;
+            const float tx = dx == 0 ? 0.5f : 0.25f;
+            const float4 Iq = I[size_t(qy) * a.w + size_t(qx)];
+            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
+            const float gw = ty * tx;
+            gs = gs + gw * Iq.w;
+            gn = gn + gw;
+        }
+    }
+    const float g = gn > 0.0f ? gs / gn : 0.0f;
+    const float den = a.sigma_luminance * sqrtf(g) + a.variance_floor;
+    const bool p_finite = finite3(V3(Ip.x, Ip.y, Ip.z));
+    const float lp = lum709(Ip.x, Ip.y, Ip.z);
+    const float zp2 = Np.w * Np.w;
+    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
+    for(int32_t dy = -2; dy <= 2; ++dy)
+    {
+        const int64_t qy = (int64_t)y + (int64_t)dy * a.step;
+        if(qy < 0 || qy >= (int64_t)a.h) continue;
+        const float hy = dy == 0 ? 0.375f : (dy == -1 || dy == 1) ? 0.25f : 0.0625f;
+        for(int32_t dx = -2; dx <= 2; ++dx)
+        {
+            const int64_t qx = (int64_t)x + (int64_t)dx * a.step;
+            if(qx < 0 || qx >= (int64_t)a.w) continue;
+            const float hx = dx == 0 ? 0.375f : (dx == -1 || dx == 1) ? 0.25f : 0.0625f;
+            const size_t q = size_t(qy) * a.w + size_t(qx);
+            const float4 Iq = I[q];
+            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
+            const float4 Aq = albedo[q], Nq = normal_depth[q];
+            const float el = p_finite ? fabsf(lp - lum709(Iq.x, Iq.y, Iq.z)) / den : 0.0f;
+            const float ax = Ap.x - Aq.x, ay = Ap.y - Aq.y, az = Ap.z - Aq.z, aw = Ap.w - Aq.w;
+            const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
+            const float nx = Np.x - Nq.x, ny = Np.y - Nq.y, nz = Np.z - Nq.z;
+            const float dn = (nx * nx + ny * ny) + nz * nz;
+            const float dz = Np.w - Nq.w;
+            const float zq2 = Nq.w * Nq.w;
+            const float zmax = (zp2 > zq2 || zp2 != zp2) ? zp2 : zq2;   // a NaN depth stays NaN
+            const float dz2 = (dz * dz) / (zmax + 1e-12f);
+            const float e = ((el + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
+            if(!__builtin_isfinite(e)) continue;
+            const float wgt = (hy * hx) * (float)dexp(-(double)e);
+            sw = sw + wgt;
+            sx = sx + wgt * Iq.x;
+            sy = sy + wgt * Iq.y;
+            sz = sz + wgt * Iq.z;
+            sv = sv + (wgt * wgt) * Iq.w;
+        }
+    }
+    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, dn_var_ok(sv / (sw * sw)))
+                       : make_float4(Ip.x, Ip.y, Ip.z, dn_var_ok(Ip.w));
+}
+
 // ---------------------------------------------------------------- runtime --
 
 struct DevBuf {
@@ -1090,6 +1254,7 @@ struct ptg_context {
     bool frame_ready = false;
     // render workspace
     DevBuf acc, tmp_a, tmp_b, tmp_c, counters;
+    DevBuf mom;                            // ptg_render_moments: the running (s1, s2, n) per pixel, beside acc
     DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
     DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
     DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
@@ -1301,6 +1466,7 @@ struct RenderJob {
     size_t spill_region = 0;               // walk stack spill entries per (slot, walk kind)
     unsigned long long* cnt = nullptr;     // counting renders: the device counters
     uint32_t prev_slot = 0xFFFFFFFFu;      // the slot of the last fold
+    float4* out_moments = nullptr;         // ptg_render_moments: the fold also keeps the luminance moments
     SlotState st[kWfSlots];
 
     unsigned long long* cnt_for(int kind) const { return cnt ? cnt + 8 * kind : nullptr; }
@@ -1461,7 +1627,9 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc)
 // GPU_MAX_HW_QUEUES = 4 queues - so a fold waiting for slot 1's chunk
 // blocked slot 0's next launches behind it: profiles/r06c_timeline/.)
 // A slot's next chunk then reuses its samples buffer after its fold in
-// stream order, with no event at all.
+// stream order, with no event at all.  A render that keeps the samples'
+// moments (ptg_render_moments) folds with k_accumulate_moments instead, in the
+// same place and order.
 int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
@@ -1470,9 +1638,16 @@ int fold_chunk(RenderJob& job, const Piece& pc)
     const hipStream_t as = ctx->main_of(pc.slot);
     if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
         PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
-    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate, k_accumulate, job.pm, pc.n,
-                      sl.samples.as<float4>(), ctx->acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
-                      job.out_accum, job.out_bgra))
+    if(job.out_moments)
+    {
+        if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate_moments, k_accumulate_moments, job.pm,
+                          pc.n, sl.samples.as<float4>(), ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last,
+                          (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
+            return r;
+    }
+    else if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate, k_accumulate, job.pm, pc.n,
+                           sl.samples.as<float4>(), ctx->acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
+                           job.out_accum, job.out_bgra))
         return r;
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
     job.prev_slot = pc.slot;
@@ -1520,7 +1695,7 @@ int read_counters(ptg_context* ctx)
 // path kernels write one float4 per (pixel, sample); k_accumulate folds the
 // chunk into the running per-pixel sum in sample order.
 int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
-               ptg_float4* out_accum, ptg_uchar4* out_bgra)
+               ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments = nullptr)
 {
     if(pm.npix == 0) return PTG_OK;
     if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
@@ -1536,6 +1711,11 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
     for(uint32_t k = 0; k < pipelines; ++k)
         PTG_HIP(ctx->grow(ctx->slot[k].samples, size_t(pm.npix) * job.chunk * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
+    if(out_moments)
+    {
+        job.out_moments = reinterpret_cast<float4*>(out_moments);
+        PTG_HIP(ctx->grow(ctx->mom, size_t(pm.npix) * sizeof(float4)));
+    }
     if(ctx->counting)
     {
         PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
@@ -1900,6 +2080,18 @@ int ptg_render(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra);
 }
 
+int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                       uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_accum, ptg_uchar4* out_bgra,
+                       ptg_float4* out_moments)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, sample_end)) return r;
+    if(!out_moments) return fail(PTG_E_INVALID, "ptg_render_moments: null out_moments");
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
+    return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments);
+}
+
 static int tile_map(const ptg_render_config* cfg, uint32_t tw, uint32_t th, uint32_t first, uint32_t stride,
                     uint32_t count, PixelMap& pm)
 {
@@ -2132,6 +2324,75 @@ int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_para
         const float sc = P.sigma_color * (1.0f / float(1u << k));   // sigma_color * 2^-k
         a.var_color = sc * sc;
         hipLaunchKernelGGL(k_dn_atrous, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, a, cur, alb,
+                           reinterpret_cast<const float4*>(normal_depth), nxt);
+        PTG_HIP(hipGetLastError());
+        std::swap(cur, nxt);
+    }
+    hipLaunchKernelGGL(k_dn_remodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, cur, alb, out,
+                       reinterpret_cast<uchar4*>(out_bgra));
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+void ptg_denoise_guided_params_default(ptg_denoise_guided_params* p)
+{
+    if(!p) return;
+    // the best row of tools/denoise_study.py --guided --sweep (profiles/denoise_study/guided_study.json)
+    p->iterations = 3;
+    p->sigma_luminance = 0.5f;
+    p->sigma_albedo = 0.05f;
+    p->sigma_normal = 1.2f;
+    p->sigma_depth = 1.0f;
+    p->albedo_floor = 0.01f;
+    p->variance_floor = 1e-2f;
+}
+
+int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_guided_params* params,
+                       const ptg_float4* radiance, const ptg_float4* albedo, const ptg_float4* normal_depth,
+                       const ptg_float4* moments, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
+{
+    if(int r = bind(ctx)) return r;
+    if(!params || !radiance || !albedo || !normal_depth || !moments || !out_radiance)
+        return fail(PTG_E_INVALID, "ptg_denoise_guided: null argument");
+    const ptg_denoise_guided_params P = *params;
+    if(P.iterations > 8) return fail(PTG_E_INVALID, "ptg_denoise_guided: more than 8 iterations");
+    for(float s: {P.sigma_luminance, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor, P.variance_floor})
+        if(!(s > 0.0f) || !std::isfinite(s))
+            return fail(PTG_E_INVALID, "ptg_denoise_guided: sigmas and floors must be positive and finite");
+    if(uint64_t(w) * h == 0) return PTG_OK;
+    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
+    const uint32_t n = w * h;
+    const float4* rad = reinterpret_cast<const float4*>(radiance);
+    const float4* alb = reinterpret_cast<const float4*>(albedo);
+    float4* out = reinterpret_cast<float4*>(out_radiance);
+    if(P.iterations == 0)
+    {   // the input bits, unchanged
+        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+        if(out_bgra)
+        {
+            hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, out, reinterpret_cast<uchar4*>(out_bgra));
+            PTG_HIP(hipGetLastError());
+        }
+        return PTG_OK;
+    }
+    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
+    float4* cur = ctx->dn_a.as<float4>();
+    float4* nxt = ctx->dn_b.as<float4>();
+    hipLaunchKernelGGL(k_dn_demodulate_guided, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, rad, alb,
+                       reinterpret_cast<const float4*>(moments), cur);
+    PTG_HIP(hipGetLastError());
+    DenoiseGuidedStep a;
+    a.w = w; a.h = h;
+    a.sigma_luminance = P.sigma_luminance;
+    a.variance_floor = P.variance_floor;
+    a.var_albedo = P.sigma_albedo * P.sigma_albedo;
+    a.var_normal = P.sigma_normal * P.sigma_normal;
+    a.var_depth = P.sigma_depth * P.sigma_depth;
+    for(uint32_t k = 0; k < P.iterations; ++k)
+    {
+        a.step = 1u << k;
+        hipLaunchKernelGGL(k_dn_atrous_guided, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, a, cur, alb,
                            reinterpret_cast<const float4*>(normal_depth), nxt);
         PTG_HIP(hipGetLastError());
         std::swap(cur, nxt);

@@ -116,3 +116,160 @@ def atrous_reference(radiance, albedo, normal_depth, params: DenoiseParams = Non
         out[..., :3] = I * m                                       # remodulate
     assert out.dtype == f32
     return out
+
+
+# ---- per-pixel sample moments and the variance-guided filter -----------------
+
+PREFILTER = (0.25, 0.5, 0.25)                    # the variance prefilter's {1/4, 1/2, 1/4}
+
+
+class DenoiseGuidedParams(C.Structure):
+    """ptg_denoise_guided_params.  ``DenoiseGuidedParams.default()`` asks the library."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float),
+                ("variance_floor", C.c_float)]
+
+    @classmethod
+    def default(cls, **overrides):
+        p = cls()
+        N.lib().ptg_denoise_guided_params_default(C.byref(p))
+        for k, v in overrides.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("ptg_denoise_guided_params has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def validate(self):
+        if self.iterations > MAX_ITERATIONS:
+            raise ValueError("iterations > %d" % MAX_ITERATIONS)
+        for k, _ in self._fields_[1:]:
+            v = getattr(self, k)
+            if not (v > 0.0 and math.isfinite(v)):
+                raise ValueError("%s must be positive and finite, got %r" % (k, v))
+
+
+def _lum(v):
+    """(0.2126f * x + 0.7152f * y) + 0.0722f * z of float32 [..., >= 3]."""
+    f32 = np.float32
+    return (f32(0.2126) * v[..., 0] + f32(0.7152) * v[..., 1]) + f32(0.0722) * v[..., 2]
+
+
+def _var_ok(v):
+    """A variance the filter may use: >= 0 and finite, else 0."""
+    return np.where((v >= 0) & np.isfinite(v), v, np.float32(0))
+
+
+def moments_reference(per_sample):
+    """ptg_render_moments' out_moments on the CPU: the samples' radiance,
+    float32 [npix, n, >= 3] in sample order, to [npix, 4] float32
+    (m1, m2, variance of the mean, number of finite samples)."""
+    f32 = np.float32
+    c = np.ascontiguousarray(per_sample, dtype=f32)
+    assert c.ndim == 3 and c.shape[2] >= 3
+    npix = c.shape[0]
+    s1 = np.zeros(npix, f32)
+    s2 = np.zeros(npix, f32)
+    n = np.zeros(npix, np.int64)
+    out = np.zeros((npix, 4), f32)
+    with np.errstate(all="ignore"):
+        for j in range(c.shape[1]):
+            fin = np.isfinite(c[:, j, :3]).all(-1)
+            L = _lum(c[:, j])
+            s1 = np.where(fin, s1 + L, s1)
+            s2 = np.where(fin, s2 + L * L, s2)
+            n += fin
+        nf = n.astype(f32)
+        m1 = s1 / nf
+        m2 = s2 / nf
+        d = m2 - m1 * m1
+        var = np.where(d > 0, d, f32(0))
+        vm = np.where(n >= 2, var / (nf - f32(1)), f32(0))
+        some = n > 0
+        out[some] = np.stack([m1, m2, vm, nf], -1)[some]
+    assert out.dtype == f32
+    return out
+
+
+def atrous_guided_reference(radiance, albedo, normal_depth, moments, params: DenoiseGuidedParams = None):
+    """ptg_denoise_guided on the CPU: [h, w, 4] float32 arrays in, the denoised
+    [h, w, 4] float32 radiance (w component 0) out."""
+    P = params if params is not None else DenoiseGuidedParams.default()
+    P.validate()
+    f32 = np.float32
+    rad = np.ascontiguousarray(radiance, dtype=f32)
+    alb = np.ascontiguousarray(albedo, dtype=f32)
+    nd = np.ascontiguousarray(normal_depth, dtype=f32)
+    mom = np.ascontiguousarray(moments, dtype=f32)
+    h, w = rad.shape[:2]
+    assert rad.shape == alb.shape == nd.shape == mom.shape == (h, w, 4)
+    if P.iterations == 0:
+        return rad.copy()
+    with np.errstate(all="ignore"):
+        m = np.maximum(alb[..., :3], f32(P.albedo_floor))
+        I = rad[..., :3] / m                                       # demodulate
+        ml = _lum(m)
+        V = _var_ok(_var_ok(mom[..., 2]) / (ml * ml))
+        sl, vf = f32(P.sigma_luminance), f32(P.variance_floor)
+        va = f32(P.sigma_albedo) * f32(P.sigma_albedo)
+        vn = f32(P.sigma_normal) * f32(P.sigma_normal)
+        vz = f32(P.sigma_depth) * f32(P.sigma_depth)
+        Z = nd[..., 3]
+        for k in range(P.iterations):
+            s = 1 << k
+            fin = np.isfinite(I).all(-1)
+            gs = np.zeros((h, w), f32)
+            gn = np.zeros((h, w), f32)
+            for dy in range(-1, 2):                                # the variance prefilter, always at distance 1
+                y0, y1 = max(0, -dy), min(h, h - dy)
+                if y0 >= y1:
+                    continue
+                for dx in range(-1, 2):
+                    x0, x1 = max(0, -dx), min(w, w - dx)
+                    if x0 >= x1:
+                        continue
+                    gw = f32(PREFILTER[dy + 1]) * f32(PREFILTER[dx + 1])
+                    ps = (slice(y0, y1), slice(x0, x1))
+                    qs = (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
+                    gs[ps] = np.where(fin[qs], gs[ps] + gw * V[qs], gs[ps])
+                    gn[ps] = np.where(fin[qs], gn[ps] + gw, gn[ps])
+            g = np.where(gn > 0, gs / gn, f32(0))
+            den = sl * np.sqrt(g) + vf
+            lum = _lum(I)
+            sw = np.zeros((h, w), f32)
+            acc = np.zeros((h, w, 3), f32)
+            sv = np.zeros((h, w), f32)
+            for dy in range(-2, 3):
+                y0, y1 = max(0, -s * dy), min(h, h - s * dy)       # rows p whose tap row is inside
+                if y0 >= y1:
+                    continue
+                for dx in range(-2, 3):
+                    x0, x1 = max(0, -s * dx), min(w, w - s * dx)
+                    if x0 >= x1:
+                        continue
+                    hw = f32(KERNEL[dy + 2]) * f32(KERNEL[dx + 2])
+                    ps = (slice(y0, y1), slice(x0, x1))
+                    qs = (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
+                    Iq = I[qs]
+                    valid = fin[qs].copy()
+                    el = np.where(fin[ps], np.abs(lum[ps] - lum[qs]) / den[ps], f32(0))
+                    d = alb[ps] - alb[qs]
+                    da = _sq3(d) + d[..., 3] * d[..., 3]
+                    dn = _sq3(nd[ps][..., :3] - nd[qs][..., :3])
+                    dz = Z[ps] - Z[qs]
+                    dz2 = (dz * dz) / (np.maximum(Z[ps] * Z[ps], Z[qs] * Z[qs]) + f32(1e-12))
+                    e = ((el + da / va) + dn / vn) + dz2 / vz
+                    valid &= np.isfinite(e)
+                    wgt = hw * _exp_neg(e, valid)
+                    sw[ps] = np.where(valid, sw[ps] + wgt, sw[ps])
+                    acc[ps] = np.where(valid[..., None], acc[ps] + wgt[..., None] * Iq, acc[ps])
+                    sv[ps] = np.where(valid, sv[ps] + (wgt * wgt) * V[qs], sv[ps])
+            some = sw > 0
+            I = np.where(some[..., None], acc / sw[..., None], I)
+            V = _var_ok(np.where(some, sv / (sw * sw), V))
+        out = np.zeros((h, w, 4), f32)
+        out[..., :3] = I * m                                       # remodulate
+    assert out.dtype == f32
+    return out

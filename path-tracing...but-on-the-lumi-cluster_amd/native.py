@@ -121,6 +121,9 @@ def lib():
         "ptg_render_features": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P]),
         "ptg_denoise_params_default": (None, [P]),
         "ptg_denoise": (I, [P, U32, U32, P, P, P, P, P, P]),
+        "ptg_render_moments": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P]),
+        "ptg_denoise_guided_params_default": (None, [P]),
+        "ptg_denoise_guided": (I, [P, U32, U32, P, P, P, P, P, P, P]),
         "ptg_counters_enable": (I, [P, I]),
         "ptg_last_counters": (I, [P, P]),
         "ptg_timing_enable": (I, [P, I]),

@@ -181,6 +181,49 @@ class GpuRenderer:
         out, bgra = self.denoise(acc, albedo, normal_depth, params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
+    # -- sample moments and the variance-guided denoiser ----------------------
+    def render_moments(self, cfg: N.RenderConfig, rect=None, samples=None, want_accum=False):
+        """render() that also keeps the samples' luminance moments
+        (ptg_render_moments): (bgra, accum or None, moments float32 [h, w, 4] =
+        (mean, second moment, variance of the mean, finite samples)).  The
+        moments are normalised by the finite samples of the range rendered.
+        Asynchronous."""
+        import torch
+        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
+        dev = torch.device("cuda", self.device)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        accum = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if want_accum else None
+        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        N.check(N.lib().ptg_render_moments(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(accum), _ptr(bgra),
+                                           _ptr(moments)), "ptg_render_moments")
+        return bgra, accum, moments
+
+    def denoise_guided(self, radiance, albedo, normal_depth, moments, params=None, want_bgra=True, out_radiance=None):
+        """ptg_denoise_guided over device float32 [h, w, 4] tensors: (denoised
+        radiance, bgra uint8 [h, w, 4] or None).  `out_radiance` may be
+        `radiance` itself.  Asynchronous."""
+        import torch
+        from .denoise import DenoiseGuidedParams
+        p = params if params is not None else DenoiseGuidedParams.default()
+        h, w = radiance.shape[:2]
+        for t in (radiance, albedo, normal_depth, moments):
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        if out_radiance is None:
+            out_radiance = torch.empty_like(radiance)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
+        N.check(N.lib().ptg_denoise_guided(self._ctx, w, h, C.byref(p), _ptr(radiance), _ptr(albedo), _ptr(normal_depth),
+                                           _ptr(moments), _ptr(out_radiance), _ptr(bgra)), "ptg_denoise_guided")
+        return out_radiance, bgra
+
+    def render_denoised_guided(self, cfg: N.RenderConfig, params=None):
+        """render_moments + render_features + denoise_guided of the whole
+        image: (bgra, denoised radiance).  Asynchronous."""
+        _, acc, moments = self.render_moments(cfg, want_accum=True)
+        albedo, normal_depth = self.render_features(cfg)
+        out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, params, want_bgra=True, out_radiance=acc)
+        return bgra, out
+
     def tonemap_device(self, colors, out_bgra):
         """tonemap_pixel over a device float32 [..., 4] tensor into a device
         uint8 [..., 4] tensor (ptg_tonemap_device; asynchronous)."""

@@ -11,7 +11,16 @@ PSNR of both frames picks the row) and uses the best row for the table; the
 library's defaults (ptg_denoise_params_default) are the best row of the
 recorded sweep.  Without --sweep the table uses the library's defaults.
 
-Usage: python tools/denoise_study.py [--sweep] [--out profiles/<name>]
+--guided studies the variance-guided filter instead (ptg_render_moments +
+ptg_denoise_guided): per row the raw, the fixed-sigma (library defaults) and
+the guided PSNR, and the HIP-event times of ptg_render, ptg_render_moments and
+the guided filter.  With --sweep it first ranks a grid of
+ptg_denoise_guided_params by the mean guided PSNR over both frames at 16, 64
+and 256 spp - one setting has to hold across sample counts - and uses the best
+row; the library's defaults (ptg_denoise_guided_params_default) are the best
+row of the recorded sweep.  Writes <out>/guided_study.json.
+
+Usage: python tools/denoise_study.py [--guided] [--sweep] [--out profiles/<name>]
 Writes <out>/denoise_study.json.
 """
 import argparse
@@ -29,7 +38,7 @@ import ptlumi_loader  # noqa: E402
 
 P = ptlumi_loader.load()
 N, V = P.native, P.validator
-from ptlumi.denoise import DenoiseParams  # noqa: E402
+from ptlumi.denoise import DenoiseGuidedParams, DenoiseParams  # noqa: E402
 
 ASSETS = os.path.join(ROOT, "assets")
 W, H = 1280, 720
@@ -63,11 +72,115 @@ def psnr_half(ref_half, bgra):
     return float(V.validate_frame(ref_half, bgra.cpu().numpy())[0])
 
 
+GUIDED_SWEEP_SPPS = (16, 64, 256)
+GUIDED_GRID = {
+    "iterations": (3, 4, 5),
+    "sigma_luminance": (0.5, 1.0, 2.0, 4.0, 8.0, 16.0),
+    "sigma_albedo": (0.05, 0.2),
+    "sigma_normal": (0.3, 1.2),
+    "variance_floor": (1e-4, 1e-3, 1e-2),
+}
+
+
+def guided_study(args):
+    r = P.GpuRenderer(0)
+    result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP},
+              "device": torch.cuda.get_device_name(0)}
+    cfg = N.RenderConfig.make(W, H, REF_SPP)
+    scene = N.Scene(ASSETS, cfg)
+    ref_half = {}
+    for i, f in enumerate(FRAMES):
+        scene.setup_frame(f)
+        r.upload(scene, include_static=i == 0)
+        bgra, _ = r.render(cfg)
+        r.synchronize()
+        ref_half[f] = V.downscale_half(V.bgra_to_rgb(bgra.cpu().numpy()))
+    scene.close()
+
+    # every (spp, frame): the render with and without the moments, timed, and the features
+    held = {}
+    for spp in SPPS:
+        cfg = N.RenderConfig.make(W, H, spp)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene, include_static=False)
+            (bgra, _), render_ms, _ = timed(lambda: r.render(cfg, want_accum=True))
+            (_, acc, mom), moments_ms, _ = timed(lambda: r.render_moments(cfg, want_accum=True))
+            alb, nd = r.render_features(cfg)
+            r.synchronize()
+            held[spp, f] = (bgra, acc, alb, nd, mom, {"render_ms": render_ms, "render_moments_ms": moments_ms})
+        scene.close()
+
+    params = DenoiseGuidedParams.default()
+    if args.sweep:
+        rows = []
+        keys = list(GUIDED_GRID)
+        cells = [(spp, f) for spp in GUIDED_SWEEP_SPPS for f in FRAMES]
+        # beside the ranking, the suite's end-to-end check of every row: frame 0 at
+        # 640x360x16 against the reference's own frame, full resolution (not ranked on)
+        golden = np.load(os.path.join(ROOT, "tests", "golden", "frame_0000_ref.npz"))["rgb"]
+        cfg = N.RenderConfig.make(640, 360, 16)
+        scene = N.Scene(ASSETS, cfg)
+        scene.setup_frame(0)
+        r.upload(scene, include_static=False)
+        e_bgra, e_acc, e_mom = r.render_moments(cfg, want_accum=True)
+        e_alb, e_nd = r.render_features(cfg)
+        r.synchronize()
+        scene.close()
+        e_raw = float(V.psnr(golden, V.bgra_to_rgb(e_bgra.cpu().numpy())))
+        for combo in itertools.product(*(GUIDED_GRID[k] for k in keys)):
+            p = DenoiseGuidedParams.default(**dict(zip(keys, combo)))
+            ps = {}
+            for spp, f in cells:
+                _, acc, alb, nd, mom, _ = held[spp, f]
+                _, bgra = r.denoise_guided(acc, alb, nd, mom, p)
+                ps["%d@%d" % (f, spp)] = psnr_half(ref_half[f], bgra)
+            _, bgra = r.denoise_guided(e_acc, e_alb, e_nd, e_mom, p)
+            rows.append(dict(zip(keys, combo), psnr=ps, mean=float(np.mean(list(ps.values()))),
+                             check_640x360x16_frame0=float(V.psnr(golden, V.bgra_to_rgb(bgra.cpu().numpy())))))
+            if len(rows) % 30 == 0:
+                print("sweep: %d rows" % len(rows), flush=True)
+        rows.sort(key=lambda x: -x["mean"])
+        best = rows[0]
+        params = DenoiseGuidedParams.default(**{k: best[k] for k in keys})
+        result["sweep"] = {"spps": GUIDED_SWEEP_SPPS, "grid": GUIDED_GRID, "fixed": {
+            k: v for k, v in params.as_dict().items() if k not in keys},
+            "raw": {"%d@%d" % (f, spp): psnr_half(ref_half[f], held[spp, f][0]) for spp, f in cells},
+            "check_640x360x16_frame0_raw": e_raw, "best": best, "rows": rows}
+        print("sweep: best", best, flush=True)
+    result["params"] = params.as_dict()
+    result["fixed_sigma_params"] = DenoiseParams.default().as_dict()
+
+    table = []
+    for spp in SPPS:
+        for f in FRAMES:
+            bgra, acc, alb, nd, mom, times = held[spp, f]
+            # the filters take a fraction of a millisecond: the mean of 20 runs back to back
+            (_, fixed), fixed_ms, _ = timed(lambda: [r.denoise(acc, alb, nd) for _ in range(20)][-1])
+            (_, guided), guided_ms, _ = timed(lambda: [r.denoise_guided(acc, alb, nd, mom, params) for _ in range(20)][-1])
+            fixed_ms, guided_ms = fixed_ms / 20, guided_ms / 20
+            row = {"spp": spp, "frame": f, "psnr_raw": psnr_half(ref_half[f], bgra),
+                   "psnr_fixed": psnr_half(ref_half[f], fixed), "psnr_guided": psnr_half(ref_half[f], guided),
+                   "denoise_ms": fixed_ms, "denoise_guided_ms": guided_ms}
+            row.update(times)
+            table.append(row)
+            print(json.dumps(row), flush=True)
+    result["table"] = table
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "guided_study.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", os.path.join(args.out, "guided_study.json"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--guided", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_study"))
     args = ap.parse_args()
+    if args.guided:
+        return guided_study(args)
     r = P.GpuRenderer(0)
     result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP},
               "device": torch.cuda.get_device_name(0)}
