@@ -5,12 +5,16 @@
 //   k_trace         path_trace_pixel for a (pixel set x sample chunk) grid,
 //                   one work-item per (pixel, sample); results to a
 //                   [sample][pixel] float4 buffer in HBM
-//   k_accumulate    baseline_render's j-ordered float32 sum over the chunk,
-//                   then (last chunk) / SPP + tonemap_pixel (main.cc:24-43)
-//   k_accumulate_moments  the same fold, keeping the samples' luminance moments too
+//   k_accumulate<MOMENTS>  baseline_render's j-ordered float32 sum over the chunk,
+//                   then (last chunk) / SPP + tonemap_pixel (main.cc:24-43);
+//                   <true> keeps the samples' luminance moments too
 //   k_sample_list   path_trace_pixel for an explicit (x, y, j) list (parity)
 //   k_rays          ray_query closest hit + shadow any-hit (parity)
 //   k_tonemap, k_scatter_tiles
+//   k_features      first-hit albedo, normal and depth
+//   k_dn_demodulate<GUIDED>, k_dn_atrous<STEP>, k_dn_remodulate
+//                   the a-trous denoisers: STEP is DenoiseStep (fixed sigmas)
+//                   or DenoiseGuidedStep (variance-guided)
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
@@ -732,53 +736,21 @@ __global__ __launch_bounds__(kBlock) void k_trace(DevScene sc, PixelMap pm, uint
     if(COUNT) flush_counters(cnt, counters, (p < pm.npix && jj < nj) ? 1u : 0u);
 }
 
-// acc[p] (+)= samples in index order; on the last chunk / spp and tonemap.
-__global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj, const float4* __restrict__ samples,
-                                                       float4* __restrict__ acc, int first, int last, float spp,
-                                                       float4* __restrict__ out_accum, uchar4* __restrict__ out_bgra)
-{
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if(p >= pm.npix) return;
-    float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if(!first)
-    {
-        const float4 a = acc[p];
-        ax = a.x; ay = a.y; az = a.z;
-    }
-    for(uint32_t j = 0; j < nj; ++j)
-    {
-        const float4 s = ld_out(samples + size_t(j) * pm.npix + p);
-        ax = ax + s.x;
-        ay = ay + s.y;
-        az = az + s.z;
-    }
-    if(!last)
-    {
-        acc[p] = make_float4(ax, ay, az, 0.f);
-        return;
-    }
-    ax = ax / spp;
-    ay = ay / spp;
-    az = az / spp;
-    uint32_t x, y;
-    const bool inside = pm.pixel(p, x, y);
-    if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
-}
-
 // Rec. 709 luminance of the moments and of the guided denoiser: three
 // products, two sums, each one float32 rounding
 __device__ __forceinline__ float lum709(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
 
-// k_accumulate with, in the same pass over the chunk, the first two
-// luminance moments of its finite samples (ptg_render_moments).  The radiance
-// sum is k_accumulate's operation for operation.  mom[p] = (s1, s2, n as
-// bits, -) carries across chunks as acc does; on the last chunk
-// out_moments[p] = (m1, m2, variance of the mean, n), normalised by n.
-__global__ __launch_bounds__(kBlock) void k_accumulate_moments(PixelMap pm, uint32_t nj, const float4* __restrict__ samples,
-                                                               float4* __restrict__ acc, float4* __restrict__ mom, int first,
-                                                               int last, float spp, float4* __restrict__ out_accum,
-                                                               uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments)
+// acc[p] (+)= samples in index order; on the last chunk / spp and tonemap.
+// MOMENTS (ptg_render_moments): in the same pass over the chunk, the first two
+// luminance moments of the finite samples too; the radiance sum is the same
+// operation for operation.  mom[p] = (s1, s2, n as bits, -) carries across
+// chunks as acc does; on the last chunk out_moments[p] = (m1, m2, variance of
+// the mean, n), normalised by n.  Without MOMENTS both pointers may be null.
+template<bool MOMENTS>
+__global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj, const float4* __restrict__ samples,
+                                                       float4* __restrict__ acc, float4* __restrict__ mom, int first,
+                                                       int last, float spp, float4* __restrict__ out_accum,
+                                                       uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if(p >= pm.npix) return;
@@ -789,8 +761,11 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_moments(PixelMap pm, uint
     {
         const float4 a = acc[p];
         ax = a.x; ay = a.y; az = a.z;
-        const float4 m = mom[p];
-        s1 = m.x; s2 = m.y; n = __float_as_uint(m.z);
+        if constexpr(MOMENTS)
+        {
+            const float4 m = mom[p];
+            s1 = m.x; s2 = m.y; n = __float_as_uint(m.z);
+        }
     }
     for(uint32_t j = 0; j < nj; ++j)
     {
@@ -798,18 +773,19 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_moments(PixelMap pm, uint
         ax = ax + s.x;
         ay = ay + s.y;
         az = az + s.z;
-        if(finite3(V3(s.x, s.y, s.z)))
-        {
-            const float L = lum709(s.x, s.y, s.z);
-            s1 = s1 + L;
-            s2 = s2 + L * L;
-            ++n;
-        }
+        if constexpr(MOMENTS)
+            if(finite3(V3(s.x, s.y, s.z)))
+            {
+                const float L = lum709(s.x, s.y, s.z);
+                s1 = s1 + L;
+                s2 = s2 + L * L;
+                ++n;
+            }
     }
     if(!last)
     {
         acc[p] = make_float4(ax, ay, az, 0.f);
-        mom[p] = make_float4(s1, s2, __uint_as_float(n), 0.f);
+        if constexpr(MOMENTS) mom[p] = make_float4(s1, s2, __uint_as_float(n), 0.f);
         return;
     }
     ax = ax / spp;
@@ -819,16 +795,19 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_moments(PixelMap pm, uint
     const bool inside = pm.pixel(p, x, y);
     if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if(inside && n > 0)
+    if constexpr(MOMENTS)
     {
-        const float nf = (float)n;
-        const float m1 = s1 / nf, m2 = s2 / nf;
-        const float d = m2 - m1 * m1;
-        const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
-        r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if(inside && n > 0)
+        {
+            const float nf = (float)n;
+            const float m1 = s1 / nf, m2 = s2 / nf;
+            const float d = m2 - m1 * m1;
+            const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
+            r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
+        }
+        out_moments[p] = r;
     }
-    out_moments[p] = r;
 }
 
 __global__ __launch_bounds__(kBlock) void k_sample_list(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
@@ -983,147 +962,88 @@ __global__ __launch_bounds__(kBlock) void k_features(DevScene sc, PixelMap pm, u
 // max(albedo, floor) of the denoiser's (de)modulation; a NaN albedo stays NaN
 __device__ __forceinline__ float dn_floor(float a, float fl) { return (a > fl || a != a) ? a : fl; }
 
-// I0 = radiance / max(albedo, floor) per channel
-__global__ __launch_bounds__(kBlock) void k_dn_demodulate(uint32_t n, float fl, const float4* __restrict__ radiance,
-                                                          const float4* __restrict__ albedo, float4* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n) return;
-    const float4 r = radiance[i], a = albedo[i];
-    out[i] = make_float4(r.x / dn_floor(a.x, fl), r.y / dn_floor(a.y, fl), r.z / dn_floor(a.z, fl), 0.0f);
-}
-
-struct DenoiseStep {
-    uint32_t w, h, step;
-    float var_color, var_albedo, var_normal, var_depth;   // sigma * sigma of this iteration
-};
-
-// One edge-avoiding a-trous iteration, one work-item per pixel: 5 x 5 taps
-// `step` pixels apart, dy outer and dx inner, every operation one float32
-// rounding in the order DESIGN.md gives; the weight's exp is glibc's.
-__global__ __launch_bounds__(kBlock) void k_dn_atrous(DenoiseStep a, const float4* __restrict__ I,
-                                                      const float4* __restrict__ albedo,
-                                                      const float4* __restrict__ normal_depth, float4* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= a.w * a.h) return;
-    const int32_t x = (int32_t)(i % a.w), y = (int32_t)(i / a.w);
-    const float4 Ip = I[i], Ap = albedo[i], Np = normal_depth[i];
-    const bool p_finite = finite3(V3(Ip.x, Ip.y, Ip.z));
-    const float zp2 = Np.w * Np.w;
-    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    for(int32_t dy = -2; dy <= 2; ++dy)
-    {
-        const int64_t qy = (int64_t)y + (int64_t)dy * a.step;
-        if(qy < 0 || qy >= (int64_t)a.h) continue;
-        const float hy = dy == 0 ? 0.375f : (dy == -1 || dy == 1) ? 0.25f : 0.0625f;
-        for(int32_t dx = -2; dx <= 2; ++dx)
-        {
-            const int64_t qx = (int64_t)x + (int64_t)dx * a.step;
-            if(qx < 0 || qx >= (int64_t)a.w) continue;
-            const float hx = dx == 0 ? 0.375f : (dx == -1 || dx == 1) ? 0.25f : 0.0625f;
-            const size_t q = size_t(qy) * a.w + size_t(qx);
-            const float4 Iq = I[q];
-            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
-            const float4 Aq = albedo[q], Nq = normal_depth[q];
-            float dc = 0.0f;
-            if(p_finite)
-            {
-                const float cx = Ip.x - Iq.x, cy = Ip.y - Iq.y, cz = Ip.z - Iq.z;
-                dc = (cx * cx + cy * cy) + cz * cz;
-            }
-            const float ax = Ap.x - Aq.x, ay = Ap.y - Aq.y, az = Ap.z - Aq.z, aw = Ap.w - Aq.w;
-            const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
-            const float nx = Np.x - Nq.x, ny = Np.y - Nq.y, nz = Np.z - Nq.z;
-            const float dn = (nx * nx + ny * ny) + nz * nz;
-            const float dz = Np.w - Nq.w;
-            const float zq2 = Nq.w * Nq.w;
-            const float zmax = (zp2 > zq2 || zp2 != zp2) ? zp2 : zq2;   // a NaN depth stays NaN
-            const float dz2 = (dz * dz) / (zmax + 1e-12f);
-            const float e = ((dc / a.var_color + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
-            if(!__builtin_isfinite(e)) continue;
-            const float wgt = (hy * hx) * (float)dexp(-(double)e);
-            sw = sw + wgt;
-            sx = sx + wgt * Iq.x;
-            sy = sy + wgt * Iq.y;
-            sz = sz + wgt * Iq.z;
-        }
-    }
-    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, 0.0f) : make_float4(Ip.x, Ip.y, Ip.z, 0.0f);
-}
-
-// out = I * max(albedo, floor), w = 0; optionally its tonemap
-__global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, const float4* __restrict__ I,
-                                                          const float4* __restrict__ albedo, float4* __restrict__ out,
-                                                          uchar4* __restrict__ out_bgra)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n) return;
-    const float4 v = I[i], a = albedo[i];
-    const f3 c = V3(v.x * dn_floor(a.x, fl), v.y * dn_floor(a.y, fl), v.z * dn_floor(a.z, fl));
-    out[i] = make_float4(c.x, c.y, c.z, 0.0f);
-    if(out_bgra) out_bgra[i] = tonemap(c);
-}
-
 // a variance the guided denoiser may use: >= 0 and finite, else 0
 __device__ __forceinline__ float dn_var_ok(float v) { return (v >= 0.0f && __builtin_isfinite(v)) ? v : 0.0f; }
 
-// ptg_denoise_guided's image: (I0, V0) = (radiance / max(albedo, floor), the
-// variance of the pixel's mean luminance (moments.z) / lum(max(albedo, floor))^2)
-__global__ __launch_bounds__(kBlock) void k_dn_demodulate_guided(uint32_t n, float fl, const float4* __restrict__ radiance,
-                                                                 const float4* __restrict__ albedo,
-                                                                 const float4* __restrict__ moments, float4* __restrict__ out)
+// I0 = radiance / max(albedo, floor) per channel.  GUIDED (ptg_denoise_guided):
+// the w lane is V0, the variance of the pixel's mean luminance (moments.z) /
+// lum(max(albedo, floor))^2; else it is 0 and moments is not read.
+template<bool GUIDED>
+__global__ __launch_bounds__(kBlock) void k_dn_demodulate(uint32_t n, float fl, const float4* __restrict__ radiance,
+                                                          const float4* __restrict__ albedo,
+                                                          const float4* __restrict__ moments, float4* __restrict__ out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= n) return;
     const float4 r = radiance[i], a = albedo[i];
     const float mx = dn_floor(a.x, fl), my = dn_floor(a.y, fl), mz = dn_floor(a.z, fl);
-    const float v = dn_var_ok(moments[i].z);
-    const float ml = lum709(mx, my, mz);
-    out[i] = make_float4(r.x / mx, r.y / my, r.z / mz, dn_var_ok(v / (ml * ml)));
+    float4 o = make_float4(r.x / mx, r.y / my, r.z / mz, 0.0f);
+    if constexpr(GUIDED)
+    {
+        const float v = dn_var_ok(moments[i].z);
+        const float ml = lum709(mx, my, mz);
+        o.w = dn_var_ok(v / (ml * ml));
+    }
+    out[i] = o;
 }
 
+// One iteration's arguments: the fixed filter's colour range (ptg_denoise) or
+// the guided filter's luminance range (ptg_denoise_guided), and what they share
+struct DenoiseStep {
+    static constexpr bool guided = false;
+    uint32_t w, h, step;
+    float var_color, var_albedo, var_normal, var_depth;   // sigma * sigma of this iteration
+};
 struct DenoiseGuidedStep {
+    static constexpr bool guided = true;
     uint32_t w, h, step;
     float sigma_luminance, variance_floor;
     float var_albedo, var_normal, var_depth;              // sigma * sigma
 };
 
-// One variance-guided a-trous iteration over (I.xyz, V), one work-item per
-// pixel: a 3 x 3 prefilter of V at distance 1 sets the luminance range, then
-// k_dn_atrous's 5 x 5 taps `step` apart filter I with the weights and V with
-// their squares.  Every operation is one float32 rounding in DESIGN.md's order.
-__global__ __launch_bounds__(kBlock) void k_dn_atrous_guided(DenoiseGuidedStep a, const float4* __restrict__ I,
-                                                             const float4* __restrict__ albedo,
-                                                             const float4* __restrict__ normal_depth,
-                                                             float4* __restrict__ out)
+// One edge-avoiding a-trous iteration, one work-item per pixel: 5 x 5 taps
+// `step` pixels apart, dy outer and dx inner, every operation one float32
+// rounding in the order DESIGN.md gives; the weight's exp is glibc's.
+// The fixed filter (STEP = DenoiseStep) compares colours against var_color.
+// The guided one (DenoiseGuidedStep) filters (I.xyz, V): a 3 x 3 prefilter of
+// V at distance 1 sets the range of the luminance difference, and the taps
+// filter V with the squares of the weights.
+template<class STEP>
+__global__ __launch_bounds__(kBlock) void k_dn_atrous(STEP a, const float4* __restrict__ I,
+                                                      const float4* __restrict__ albedo,
+                                                      const float4* __restrict__ normal_depth, float4* __restrict__ out)
 {
+    constexpr bool GUIDED = STEP::guided;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= a.w * a.h) return;
     const int32_t x = (int32_t)(i % a.w), y = (int32_t)(i / a.w);
     const float4 Ip = I[i], Ap = albedo[i], Np = normal_depth[i];
-    float gs = 0.0f, gn = 0.0f;
-    for(int32_t dy = -1; dy <= 1; ++dy)
+    float den = 0.0f, lp = 0.0f;
+    if constexpr(GUIDED)
     {
-        const int32_t qy = y + dy;
-        if(qy < 0 || qy >= (int32_t)a.h) continue;
-        const float ty = dy == 0 ? 0.5f : 0.25f;
-        for(int32_t dx = -1; dx <= 1; ++dx)
+        float gs = 0.0f, gn = 0.0f;
+        for(int32_t dy = -1; dy <= 1; ++dy)
         {
-            const int32_t qx = x + dx;
-            if(qx < 0 || qx >= (int32_t)a.w) continue;
-            const float tx = dx == 0 ? 0.5f : 0.25f;
-            const float4 Iq = I[size_t(qy) * a.w + size_t(qx)];
-            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
-            const float gw = ty * tx;
-            gs = gs + gw * Iq.w;
-            gn = gn + gw;
+            const int32_t qy = y + dy;
+            if(qy < 0 || qy >= (int32_t)a.h) continue;
+            const float ty = dy == 0 ? 0.5f : 0.25f;
+            for(int32_t dx = -1; dx <= 1; ++dx)
+            {
+                const int32_t qx = x + dx;
+                if(qx < 0 || qx >= (int32_t)a.w) continue;
+                const float tx = dx == 0 ? 0.5f : 0.25f;
+                const float4 Iq = I[size_t(qy) * a.w + size_t(qx)];
+                if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
+                const float gw = ty * tx;
+                gs = gs + gw * Iq.w;
+                gn = gn + gw;
+            }
         }
+        const float g = gn > 0.0f ? gs / gn : 0.0f;
+        den = a.sigma_luminance * sqrtf(g) + a.variance_floor;
+        lp = lum709(Ip.x, Ip.y, Ip.z);
     }
-    const float g = gn > 0.0f ? gs / gn : 0.0f;
-    const float den = a.sigma_luminance * sqrtf(g) + a.variance_floor;
     const bool p_finite = finite3(V3(Ip.x, Ip.y, Ip.z));
-    const float lp = lum709(Ip.x, Ip.y, Ip.z);
     const float zp2 = Np.w * Np.w;
     float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
     for(int32_t dy = -2; dy <= 2; ++dy)
@@ -1140,7 +1060,19 @@ __global__ __launch_bounds__(kBlock) void k_dn_atrous_guided(DenoiseGuidedStep a
             const float4 Iq = I[q];
             if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
             const float4 Aq = albedo[q], Nq = normal_depth[q];
-            const float el = p_finite ? fabsf(lp - lum709(Iq.x, Iq.y, Iq.z)) / den : 0.0f;
+            float ec = 0.0f;                                            // the colour or luminance term
+            if constexpr(GUIDED)
+                ec = p_finite ? fabsf(lp - lum709(Iq.x, Iq.y, Iq.z)) / den : 0.0f;
+            else
+            {
+                float dc = 0.0f;
+                if(p_finite)
+                {
+                    const float cx = Ip.x - Iq.x, cy = Ip.y - Iq.y, cz = Ip.z - Iq.z;
+                    dc = (cx * cx + cy * cy) + cz * cz;
+                }
+                ec = dc / a.var_color;
+            }
             const float ax = Ap.x - Aq.x, ay = Ap.y - Aq.y, az = Ap.z - Aq.z, aw = Ap.w - Aq.w;
             const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
             const float nx = Np.x - Nq.x, ny = Np.y - Nq.y, nz = Np.z - Nq.z;
@@ -1149,18 +1081,32 @@ __global__ __launch_bounds__(kBlock) void k_dn_atrous_guided(DenoiseGuidedStep a
             const float zq2 = Nq.w * Nq.w;
             const float zmax = (zp2 > zq2 || zp2 != zp2) ? zp2 : zq2;   // a NaN depth stays NaN
             const float dz2 = (dz * dz) / (zmax + 1e-12f);
-            const float e = ((el + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
+            const float e = ((ec + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
             if(!__builtin_isfinite(e)) continue;
             const float wgt = (hy * hx) * (float)dexp(-(double)e);
             sw = sw + wgt;
             sx = sx + wgt * Iq.x;
             sy = sy + wgt * Iq.y;
             sz = sz + wgt * Iq.z;
-            sv = sv + (wgt * wgt) * Iq.w;
+            if constexpr(GUIDED) sv = sv + (wgt * wgt) * Iq.w;
         }
     }
-    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, dn_var_ok(sv / (sw * sw)))
-                       : make_float4(Ip.x, Ip.y, Ip.z, dn_var_ok(Ip.w));
+    // the w lane: the guided filter's variance, else 0
+    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, GUIDED ? dn_var_ok(sv / (sw * sw)) : 0.0f)
+                       : make_float4(Ip.x, Ip.y, Ip.z, GUIDED ? dn_var_ok(Ip.w) : 0.0f);
+}
+
+// out = I * max(albedo, floor), w = 0; optionally its tonemap
+__global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, const float4* __restrict__ I,
+                                                          const float4* __restrict__ albedo, float4* __restrict__ out,
+                                                          uchar4* __restrict__ out_bgra)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n) return;
+    const float4 v = I[i], a = albedo[i];
+    const f3 c = V3(v.x * dn_floor(a.x, fl), v.y * dn_floor(a.y, fl), v.z * dn_floor(a.z, fl));
+    out[i] = make_float4(c.x, c.y, c.z, 0.0f);
+    if(out_bgra) out_bgra[i] = tonemap(c);
 }
 
 // ---------------------------------------------------------------- runtime --
@@ -1449,6 +1395,17 @@ int launch(ptg_context* ctx, int kind, hipStream_t st, dim3 grid, uint32_t lds, 
     return timed_end(ctx, st);
 }
 
+// A launch of the other entry points, on ctx->stream, its launch error
+// checked: neither timed nor counted (ptg_last_kernel_times lists the render
+// path alone).  `blocks` of kBlock work-items: grid_for(n) for one per element.
+template<typename... P, typename... A>
+int launch_plain(ptg_context* ctx, uint32_t blocks, void (*kernel)(P...), const A&... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, args...);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
 // A render call's fixed parts, shared by the steps render_map is made of.
 struct RenderJob {
     ptg_context* ctx;
@@ -1628,8 +1585,9 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc)
 // blocked slot 0's next launches behind it: profiles/r06c_timeline/.)
 // A slot's next chunk then reuses its samples buffer after its fold in
 // stream order, with no event at all.  A render that keeps the samples'
-// moments (ptg_render_moments) folds with k_accumulate_moments instead, in the
-// same place and order.
+// moments (ptg_render_moments) folds with k_accumulate<true>, in the same
+// place and order; k_accumulate<false> touches neither ctx->mom nor the
+// null out_moments.
 int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
@@ -1638,16 +1596,10 @@ int fold_chunk(RenderJob& job, const Piece& pc)
     const hipStream_t as = ctx->main_of(pc.slot);
     if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
         PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
-    if(job.out_moments)
-    {
-        if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate_moments, k_accumulate_moments, job.pm,
-                          pc.n, sl.samples.as<float4>(), ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last,
-                          (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
-            return r;
-    }
-    else if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, k_accumulate, k_accumulate, job.pm, pc.n,
-                           sl.samples.as<float4>(), ctx->acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
-                           job.out_accum, job.out_bgra))
+    const auto fold = job.out_moments ? k_accumulate<true> : k_accumulate<false>;
+    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(),
+                      ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
+                      job.out_accum, job.out_bgra, job.out_moments))
         return r;
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
     job.prev_slot = pc.slot;
@@ -1749,6 +1701,46 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
     if(int r = check_debug_tallies(ctx)) return r;
 #endif
     return ctx->counting ? read_counters(ctx) : PTG_OK;
+}
+
+// What ptg_denoise and ptg_denoise_guided do once their parameters are
+// checked: demodulate into dn_a, `iterations` a-trous passes between dn_a and
+// dn_b with the step record step_of(k) (a DenoiseStep or a DenoiseGuidedStep,
+// which selects the kernels), remodulate into out_radiance.  `moments` is read
+// by the guided demodulate alone.
+template<class F>
+int denoise_passes(ptg_context* ctx, uint32_t w, uint32_t h, uint32_t iterations, float albedo_floor, F step_of,
+                   const ptg_float4* radiance, const ptg_float4* albedo, const ptg_float4* normal_depth,
+                   const ptg_float4* moments, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
+{
+    using Step = decltype(step_of(0u));
+    if(uint64_t(w) * h == 0) return PTG_OK;
+    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
+    const uint32_t n = w * h;
+    const float4* rad = reinterpret_cast<const float4*>(radiance);
+    const float4* alb = reinterpret_cast<const float4*>(albedo);
+    float4* out = reinterpret_cast<float4*>(out_radiance);
+    uchar4* bgra = reinterpret_cast<uchar4*>(out_bgra);
+    if(iterations == 0)
+    {   // the input bits, unchanged
+        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+        return bgra ? launch_plain(ctx, grid_for(n), k_tonemap, n, out, bgra) : PTG_OK;
+    }
+    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
+    float4* cur = ctx->dn_a.as<float4>();
+    float4* nxt = ctx->dn_b.as<float4>();
+    if(int r = launch_plain(ctx, grid_for(n), k_dn_demodulate<Step::guided>, n, albedo_floor, rad, alb,
+                            reinterpret_cast<const float4*>(moments), cur))
+        return r;
+    for(uint32_t k = 0; k < iterations; ++k)
+    {
+        if(int r = launch_plain(ctx, grid_for(n), k_dn_atrous<Step>, step_of(k), cur, alb,
+                                reinterpret_cast<const float4*>(normal_depth), nxt))
+            return r;
+        std::swap(cur, nxt);
+    }
+    return launch_plain(ctx, grid_for(n), k_dn_remodulate, n, albedo_floor, cur, alb, out, bgra);
 }
 
 } // namespace
@@ -2127,10 +2119,8 @@ int ptg_scatter_tiles(ptg_context* ctx, const ptg_render_config* cfg, uint32_t t
     PixelMap pm;
     if(int r = tile_map(cfg, tile_w, tile_h, first_tile, tile_stride, tile_count, pm)) return r;
     if(pm.npix == 0) return PTG_OK;
-    hipLaunchKernelGGL(k_scatter_tiles, dim3(grid_for(pm.npix)), dim3(kBlock), 0, ctx->stream, pm,
-                       reinterpret_cast<const uchar4*>(tiles), reinterpret_cast<uchar4*>(image));
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
+    return launch_plain(ctx, grid_for(pm.npix), k_scatter_tiles, pm, reinterpret_cast<const uchar4*>(tiles),
+                        reinterpret_cast<uchar4*>(image));
 }
 
 // An explicit (pixel, sample) list: checked against the image and the frame's
@@ -2163,9 +2153,9 @@ int ptg_path_trace_samples(ptg_context* ctx, const ptg_render_config* cfg, size_
     if(int r = upload_sample_list(ctx, cfg, n, xy, sample_index)) return r;
     if(ctx->stack_bound >= PrivStack::kCap) return fail(PTG_E_RANGE, "walk stack bound above the per-sample kernel's stack");
     PTG_HIP(ctx->grow(ctx->tmp_c, n * sizeof(float4)));
-    hipLaunchKernelGGL(k_sample_list, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(cfg), uint32_t(n),
-                       ctx->tmp_a.as<uint2>(), ctx->tmp_b.as<int32_t>(), ctx->tmp_c.as<float4>());
-    PTG_HIP(hipGetLastError());
+    if(int r = launch_plain(ctx, grid_for(n), k_sample_list, ctx->scene_args(cfg), uint32_t(n), ctx->tmp_a.as<uint2>(),
+                            ctx->tmp_b.as<int32_t>(), ctx->tmp_c.as<float4>()))
+        return r;
     PTG_HIP(hipMemcpyAsync(out, ctx->tmp_c.p, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
     return PTG_OK;
@@ -2176,10 +2166,8 @@ int ptg_tonemap_device(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_
     if(int r = bind(ctx)) return r;
     if(!n) return PTG_OK;
     if(!color || !out || n >= (1u << 31)) return fail(PTG_E_INVALID, "ptg_tonemap_device: bad arguments");
-    hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, uint32_t(n),
-                       reinterpret_cast<const float4*>(color), reinterpret_cast<uchar4*>(out));
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
+    return launch_plain(ctx, grid_for(n), k_tonemap, uint32_t(n), reinterpret_cast<const float4*>(color),
+                        reinterpret_cast<uchar4*>(out));
 }
 
 int ptg_tonemap(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_uchar4* out)
@@ -2190,9 +2178,7 @@ int ptg_tonemap(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_uchar4*
     PTG_HIP(ctx->grow(ctx->tmp_c, n * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->tmp_a, n * sizeof(uchar4)));
     PTG_HIP(hipMemcpyAsync(ctx->tmp_c.p, color, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, uint32_t(n), ctx->tmp_c.as<float4>(),
-                       ctx->tmp_a.as<uchar4>());
-    PTG_HIP(hipGetLastError());
+    if(int r = launch_plain(ctx, grid_for(n), k_tonemap, uint32_t(n), ctx->tmp_c.as<float4>(), ctx->tmp_a.as<uchar4>())) return r;
     PTG_HIP(hipMemcpyAsync(out, ctx->tmp_a.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
     return PTG_OK;
@@ -2219,9 +2205,9 @@ int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* r
     PTG_HIP(ctx->grow(ctx->tmp_b, n * 32));
     PTG_HIP(hipMemcpyAsync(ctx->tmp_a.p, rays, n * 32, hipMemcpyHostToDevice, ctx->stream));
     if(ctx->stack_bound >= PrivStack::kCap) return fail(PTG_E_RANGE, "walk stack bound above the per-ray kernels' stack");
-    hipLaunchKernelGGL(k_rays, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(nullptr),
-                       ctx->host_tlas_root[subframe], uint32_t(n), ctx->tmp_a.as<float>(), ctx->tmp_b.as<uint32_t>());
-    PTG_HIP(hipGetLastError());
+    if(int r = launch_plain(ctx, grid_for(n), k_rays, ctx->scene_args(nullptr), ctx->host_tlas_root[subframe], uint32_t(n),
+                            ctx->tmp_a.as<float>(), ctx->tmp_b.as<uint32_t>()))
+        return r;
     PTG_HIP(hipMemcpyAsync(hits, ctx->tmp_b.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
     return PTG_OK;
@@ -2238,9 +2224,9 @@ int ptg_camera_rays(ptg_context* ctx, const ptg_render_config* cfg, size_t n, co
     PTG_HIP(ctx->grow(ctx->tmp_c, n * 36));            // n rays of 8 floats, then n subframe indices
     float* d_rays = ctx->tmp_c.as<float>();
     uint32_t* d_sub = reinterpret_cast<uint32_t*>(d_rays + n * 8);
-    hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, ctx->scene_args(cfg), uint32_t(n),
-                       ctx->tmp_a.as<uint2>(), ctx->tmp_b.as<int32_t>(), d_rays, d_sub);
-    PTG_HIP(hipGetLastError());
+    if(int r = launch_plain(ctx, grid_for(n), k_camera_rays, ctx->scene_args(cfg), uint32_t(n), ctx->tmp_a.as<uint2>(),
+                            ctx->tmp_b.as<int32_t>(), d_rays, d_sub))
+        return r;
     PTG_HIP(hipMemcpyAsync(rays, d_rays, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipMemcpyAsync(subframe, d_sub, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
@@ -2263,11 +2249,8 @@ int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t
     PTG_HIP(ctx->grow(ctx->feat_spill, std::max<size_t>(1, size_t(grid) * kBlock * ctx->stack_bound) * sizeof(uint2)));
     DevScene sc = ctx->scene_args(cfg);
     sc.spill = ctx->feat_spill.as<uint2>();
-    hipLaunchKernelGGL(k_features, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, pm,
-                       sample_begin, sample_end, (float)cfg->samples_per_pixel, reinterpret_cast<float4*>(out_albedo),
-                       reinterpret_cast<float4*>(out_normal_depth));
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
+    return launch_plain(ctx, grid, k_features, sc, pm, sample_begin, sample_end, (float)cfg->samples_per_pixel,
+                        reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth));
 }
 
 void ptg_denoise_params_default(ptg_denoise_params* p)
@@ -2291,47 +2274,18 @@ int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_para
     if(P.iterations > 8) return fail(PTG_E_INVALID, "ptg_denoise: more than 8 iterations");
     for(float s: {P.sigma_color, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor})
         if(!(s > 0.0f) || !std::isfinite(s)) return fail(PTG_E_INVALID, "ptg_denoise: sigmas and albedo_floor must be positive and finite");
-    if(uint64_t(w) * h == 0) return PTG_OK;
-    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
-    const uint32_t n = w * h;
-    const float4* rad = reinterpret_cast<const float4*>(radiance);
-    const float4* alb = reinterpret_cast<const float4*>(albedo);
-    float4* out = reinterpret_cast<float4*>(out_radiance);
-    if(P.iterations == 0)
-    {   // the input bits, unchanged
-        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-        if(out_bgra)
-        {
-            hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, out, reinterpret_cast<uchar4*>(out_bgra));
-            PTG_HIP(hipGetLastError());
-        }
-        return PTG_OK;
-    }
-    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
-    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
-    float4* cur = ctx->dn_a.as<float4>();
-    float4* nxt = ctx->dn_b.as<float4>();
-    hipLaunchKernelGGL(k_dn_demodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, rad, alb, cur);
-    PTG_HIP(hipGetLastError());
-    DenoiseStep a;
-    a.w = w; a.h = h;
-    a.var_albedo = P.sigma_albedo * P.sigma_albedo;
-    a.var_normal = P.sigma_normal * P.sigma_normal;
-    a.var_depth = P.sigma_depth * P.sigma_depth;
-    for(uint32_t k = 0; k < P.iterations; ++k)
-    {
-        a.step = 1u << k;
+    const auto step_of = [&](uint32_t k) {
+        DenoiseStep a;
+        a.w = w; a.h = h; a.step = 1u << k;
         const float sc = P.sigma_color * (1.0f / float(1u << k));   // sigma_color * 2^-k
         a.var_color = sc * sc;
-        hipLaunchKernelGGL(k_dn_atrous, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, a, cur, alb,
-                           reinterpret_cast<const float4*>(normal_depth), nxt);
-        PTG_HIP(hipGetLastError());
-        std::swap(cur, nxt);
-    }
-    hipLaunchKernelGGL(k_dn_remodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, cur, alb, out,
-                       reinterpret_cast<uchar4*>(out_bgra));
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
+        a.var_albedo = P.sigma_albedo * P.sigma_albedo;
+        a.var_normal = P.sigma_normal * P.sigma_normal;
+        a.var_depth = P.sigma_depth * P.sigma_depth;
+        return a;
+    };
+    return denoise_passes(ctx, w, h, P.iterations, P.albedo_floor, step_of, radiance, albedo, normal_depth, nullptr, out_radiance,
+                          out_bgra);
 }
 
 void ptg_denoise_guided_params_default(ptg_denoise_guided_params* p)
@@ -2359,48 +2313,18 @@ int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoi
     for(float s: {P.sigma_luminance, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor, P.variance_floor})
         if(!(s > 0.0f) || !std::isfinite(s))
             return fail(PTG_E_INVALID, "ptg_denoise_guided: sigmas and floors must be positive and finite");
-    if(uint64_t(w) * h == 0) return PTG_OK;
-    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
-    const uint32_t n = w * h;
-    const float4* rad = reinterpret_cast<const float4*>(radiance);
-    const float4* alb = reinterpret_cast<const float4*>(albedo);
-    float4* out = reinterpret_cast<float4*>(out_radiance);
-    if(P.iterations == 0)
-    {   // the input bits, unchanged
-        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-        if(out_bgra)
-        {
-            hipLaunchKernelGGL(k_tonemap, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, out, reinterpret_cast<uchar4*>(out_bgra));
-            PTG_HIP(hipGetLastError());
-        }
-        return PTG_OK;
-    }
-    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
-    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
-    float4* cur = ctx->dn_a.as<float4>();
-    float4* nxt = ctx->dn_b.as<float4>();
-    hipLaunchKernelGGL(k_dn_demodulate_guided, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, rad, alb,
-                       reinterpret_cast<const float4*>(moments), cur);
-    PTG_HIP(hipGetLastError());
-    DenoiseGuidedStep a;
-    a.w = w; a.h = h;
-    a.sigma_luminance = P.sigma_luminance;
-    a.variance_floor = P.variance_floor;
-    a.var_albedo = P.sigma_albedo * P.sigma_albedo;
-    a.var_normal = P.sigma_normal * P.sigma_normal;
-    a.var_depth = P.sigma_depth * P.sigma_depth;
-    for(uint32_t k = 0; k < P.iterations; ++k)
-    {
-        a.step = 1u << k;
-        hipLaunchKernelGGL(k_dn_atrous_guided, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, a, cur, alb,
-                           reinterpret_cast<const float4*>(normal_depth), nxt);
-        PTG_HIP(hipGetLastError());
-        std::swap(cur, nxt);
-    }
-    hipLaunchKernelGGL(k_dn_remodulate, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n, P.albedo_floor, cur, alb, out,
-                       reinterpret_cast<uchar4*>(out_bgra));
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
+    const auto step_of = [&](uint32_t k) {
+        DenoiseGuidedStep a;
+        a.w = w; a.h = h; a.step = 1u << k;
+        a.sigma_luminance = P.sigma_luminance;
+        a.variance_floor = P.variance_floor;
+        a.var_albedo = P.sigma_albedo * P.sigma_albedo;
+        a.var_normal = P.sigma_normal * P.sigma_normal;
+        a.var_depth = P.sigma_depth * P.sigma_depth;
+        return a;
+    };
+    return denoise_passes(ctx, w, h, P.iterations, P.albedo_floor, step_of, radiance, albedo, normal_depth, moments, out_radiance,
+                          out_bgra);
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

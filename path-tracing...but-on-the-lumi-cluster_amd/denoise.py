@@ -21,18 +21,17 @@ KERNEL = (0.0625, 0.25, 0.375, 0.25, 0.0625)     # the B3 spline {1/16, 1/4, 3/8
 MAX_ITERATIONS = 8
 
 
-class DenoiseParams(C.Structure):
-    """ptg_denoise_params.  ``DenoiseParams.default()`` asks the library."""
-    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
+class _Params:
+    """What the two parameter structures share; each names the library's
+    default function and its fields that must be positive and finite."""
 
     @classmethod
     def default(cls, **overrides):
         p = cls()
-        N.lib().ptg_denoise_params_default(C.byref(p))
+        getattr(N.lib(), cls._default_fn)(C.byref(p))
         for k, v in overrides.items():
             if k not in dict(cls._fields_):
-                raise TypeError("ptg_denoise_params has no field %r" % k)
+                raise TypeError("%s has no field %r" % (cls._default_fn[:-len("_default")], k))
             setattr(p, k, v)
         return p
 
@@ -42,10 +41,18 @@ class DenoiseParams(C.Structure):
     def validate(self):
         if self.iterations > MAX_ITERATIONS:
             raise ValueError("iterations > %d" % MAX_ITERATIONS)
-        for k in ("sigma_color", "sigma_albedo", "sigma_normal", "sigma_depth", "albedo_floor"):
+        for k in self._positive:
             v = getattr(self, k)
             if not (v > 0.0 and math.isfinite(v)):
                 raise ValueError("%s must be positive and finite, got %r" % (k, v))
+
+
+class DenoiseParams(_Params, C.Structure):
+    """ptg_denoise_params.  ``DenoiseParams.default()`` asks the library."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
+    _default_fn = "ptg_denoise_params_default"
+    _positive = ("sigma_color", "sigma_albedo", "sigma_normal", "sigma_depth", "albedo_floor")
 
 
 def _sq3(d):
@@ -59,6 +66,51 @@ def _exp_neg(e, valid):
     for i in np.nonzero(flat_v)[0]:
         flat_o[i] = math.exp(-float(flat_e[i]))
     return out.astype(np.float32)
+
+
+def _atrous_taps(I, alb, nd, s, P, colour_term, V=None):
+    """One iteration's 5 x 5 taps `s` apart over I [h, w, 3], dy outer and dx
+    inner: (sw, acc, sv), the sums of the weights, of weight * I and, with the
+    variance plane V, of weight^2 * V (else None).  ``colour_term(ps, qs)`` is
+    the exponent's first term between the pixels ps and their taps qs, where
+    the pixel is finite; the albedo, normal and depth terms, the finiteness
+    rules and the weight are the two filters' common definition."""
+    f32 = np.float32
+    h, w = I.shape[:2]
+    va = f32(P.sigma_albedo) * f32(P.sigma_albedo)
+    vn = f32(P.sigma_normal) * f32(P.sigma_normal)
+    vz = f32(P.sigma_depth) * f32(P.sigma_depth)
+    Z = nd[..., 3]
+    fin = np.isfinite(I).all(-1)
+    sw = np.zeros((h, w), f32)
+    acc = np.zeros((h, w, 3), f32)
+    sv = np.zeros((h, w), f32) if V is not None else None
+    for dy in range(-2, 3):
+        y0, y1 = max(0, -s * dy), min(h, h - s * dy)               # rows p whose tap row is inside
+        if y0 >= y1:
+            continue
+        for dx in range(-2, 3):
+            x0, x1 = max(0, -s * dx), min(w, w - s * dx)
+            if x0 >= x1:
+                continue
+            hw = f32(KERNEL[dy + 2]) * f32(KERNEL[dx + 2])
+            ps = (slice(y0, y1), slice(x0, x1))
+            qs = (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
+            valid = fin[qs].copy()
+            ec = np.where(fin[ps], colour_term(ps, qs), f32(0))
+            d = alb[ps] - alb[qs]
+            da = _sq3(d) + d[..., 3] * d[..., 3]
+            dn = _sq3(nd[ps][..., :3] - nd[qs][..., :3])
+            dz = Z[ps] - Z[qs]
+            dz2 = (dz * dz) / (np.maximum(Z[ps] * Z[ps], Z[qs] * Z[qs]) + f32(1e-12))
+            e = ((ec + da / va) + dn / vn) + dz2 / vz
+            valid &= np.isfinite(e)
+            wgt = hw * _exp_neg(e, valid)
+            sw[ps] = np.where(valid, sw[ps] + wgt, sw[ps])
+            acc[ps] = np.where(valid[..., None], acc[ps] + wgt[..., None] * I[qs], acc[ps])
+            if V is not None:
+                sv[ps] = np.where(valid, sv[ps] + (wgt * wgt) * V[qs], sv[ps])
+    return sw, acc, sv
 
 
 def atrous_reference(radiance, albedo, normal_depth, params: DenoiseParams = None):
@@ -77,40 +129,10 @@ def atrous_reference(radiance, albedo, normal_depth, params: DenoiseParams = Non
     with np.errstate(all="ignore"):
         m = np.maximum(alb[..., :3], f32(P.albedo_floor))
         I = rad[..., :3] / m                                       # demodulate
-        va = f32(P.sigma_albedo) * f32(P.sigma_albedo)
-        vn = f32(P.sigma_normal) * f32(P.sigma_normal)
-        vz = f32(P.sigma_depth) * f32(P.sigma_depth)
-        Z = nd[..., 3]
         for k in range(P.iterations):
-            s = 1 << k
             sc = f32(P.sigma_color) * f32(2.0 ** -k)
             vc = sc * sc
-            sw = np.zeros((h, w), f32)
-            acc = np.zeros((h, w, 3), f32)
-            for dy in range(-2, 3):
-                y0, y1 = max(0, -s * dy), min(h, h - s * dy)       # rows p whose tap row is inside
-                if y0 >= y1:
-                    continue
-                for dx in range(-2, 3):
-                    x0, x1 = max(0, -s * dx), min(w, w - s * dx)
-                    if x0 >= x1:
-                        continue
-                    hw = f32(KERNEL[dy + 2]) * f32(KERNEL[dx + 2])
-                    ps = (slice(y0, y1), slice(x0, x1))
-                    qs = (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
-                    Ip, Iq = I[ps], I[qs]
-                    valid = np.isfinite(Iq).all(-1)
-                    dc = np.where(np.isfinite(Ip).all(-1), _sq3(Ip - Iq), f32(0))
-                    d = alb[ps] - alb[qs]
-                    da = _sq3(d) + d[..., 3] * d[..., 3]
-                    dn = _sq3(nd[ps][..., :3] - nd[qs][..., :3])
-                    dz = Z[ps] - Z[qs]
-                    dz2 = (dz * dz) / (np.maximum(Z[ps] * Z[ps], Z[qs] * Z[qs]) + f32(1e-12))
-                    e = ((dc / vc + da / va) + dn / vn) + dz2 / vz
-                    valid &= np.isfinite(e)
-                    wgt = hw * _exp_neg(e, valid)
-                    sw[ps] = np.where(valid, sw[ps] + wgt, sw[ps])
-                    acc[ps] = np.where(valid[..., None], acc[ps] + wgt[..., None] * Iq, acc[ps])
+            sw, acc, _ = _atrous_taps(I, alb, nd, 1 << k, P, lambda ps, qs: _sq3(I[ps] - I[qs]) / vc)
             I = np.where((sw > 0)[..., None], acc / sw[..., None], I)
         out = np.zeros((h, w, 4), f32)
         out[..., :3] = I * m                                       # remodulate
@@ -123,32 +145,13 @@ def atrous_reference(radiance, albedo, normal_depth, params: DenoiseParams = Non
 PREFILTER = (0.25, 0.5, 0.25)                    # the variance prefilter's {1/4, 1/2, 1/4}
 
 
-class DenoiseGuidedParams(C.Structure):
+class DenoiseGuidedParams(_Params, C.Structure):
     """ptg_denoise_guided_params.  ``DenoiseGuidedParams.default()`` asks the library."""
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_albedo", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float),
                 ("variance_floor", C.c_float)]
-
-    @classmethod
-    def default(cls, **overrides):
-        p = cls()
-        N.lib().ptg_denoise_guided_params_default(C.byref(p))
-        for k, v in overrides.items():
-            if k not in dict(cls._fields_):
-                raise TypeError("ptg_denoise_guided_params has no field %r" % k)
-            setattr(p, k, v)
-        return p
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-    def validate(self):
-        if self.iterations > MAX_ITERATIONS:
-            raise ValueError("iterations > %d" % MAX_ITERATIONS)
-        for k, _ in self._fields_[1:]:
-            v = getattr(self, k)
-            if not (v > 0.0 and math.isfinite(v)):
-                raise ValueError("%s must be positive and finite, got %r" % (k, v))
+    _default_fn = "ptg_denoise_guided_params_default"
+    _positive = ("sigma_luminance", "sigma_albedo", "sigma_normal", "sigma_depth", "albedo_floor", "variance_floor")
 
 
 def _lum(v):
@@ -213,12 +216,7 @@ def atrous_guided_reference(radiance, albedo, normal_depth, moments, params: Den
         ml = _lum(m)
         V = _var_ok(_var_ok(mom[..., 2]) / (ml * ml))
         sl, vf = f32(P.sigma_luminance), f32(P.variance_floor)
-        va = f32(P.sigma_albedo) * f32(P.sigma_albedo)
-        vn = f32(P.sigma_normal) * f32(P.sigma_normal)
-        vz = f32(P.sigma_depth) * f32(P.sigma_depth)
-        Z = nd[..., 3]
         for k in range(P.iterations):
-            s = 1 << k
             fin = np.isfinite(I).all(-1)
             gs = np.zeros((h, w), f32)
             gn = np.zeros((h, w), f32)
@@ -238,34 +236,7 @@ def atrous_guided_reference(radiance, albedo, normal_depth, moments, params: Den
             g = np.where(gn > 0, gs / gn, f32(0))
             den = sl * np.sqrt(g) + vf
             lum = _lum(I)
-            sw = np.zeros((h, w), f32)
-            acc = np.zeros((h, w, 3), f32)
-            sv = np.zeros((h, w), f32)
-            for dy in range(-2, 3):
-                y0, y1 = max(0, -s * dy), min(h, h - s * dy)       # rows p whose tap row is inside
-                if y0 >= y1:
-                    continue
-                for dx in range(-2, 3):
-                    x0, x1 = max(0, -s * dx), min(w, w - s * dx)
-                    if x0 >= x1:
-                        continue
-                    hw = f32(KERNEL[dy + 2]) * f32(KERNEL[dx + 2])
-                    ps = (slice(y0, y1), slice(x0, x1))
-                    qs = (slice(y0 + s * dy, y1 + s * dy), slice(x0 + s * dx, x1 + s * dx))
-                    Iq = I[qs]
-                    valid = fin[qs].copy()
-                    el = np.where(fin[ps], np.abs(lum[ps] - lum[qs]) / den[ps], f32(0))
-                    d = alb[ps] - alb[qs]
-                    da = _sq3(d) + d[..., 3] * d[..., 3]
-                    dn = _sq3(nd[ps][..., :3] - nd[qs][..., :3])
-                    dz = Z[ps] - Z[qs]
-                    dz2 = (dz * dz) / (np.maximum(Z[ps] * Z[ps], Z[qs] * Z[qs]) + f32(1e-12))
-                    e = ((el + da / va) + dn / vn) + dz2 / vz
-                    valid &= np.isfinite(e)
-                    wgt = hw * _exp_neg(e, valid)
-                    sw[ps] = np.where(valid, sw[ps] + wgt, sw[ps])
-                    acc[ps] = np.where(valid[..., None], acc[ps] + wgt[..., None] * Iq, acc[ps])
-                    sv[ps] = np.where(valid, sv[ps] + (wgt * wgt) * V[qs], sv[ps])
+            sw, acc, sv = _atrous_taps(I, alb, nd, 1 << k, P, lambda ps, qs: np.abs(lum[ps] - lum[qs]) / den[ps], V)
             some = sw > 0
             I = np.where(some[..., None], acc / sw[..., None], I)
             V = _var_ok(np.where(some, sv / (sw * sw), V))

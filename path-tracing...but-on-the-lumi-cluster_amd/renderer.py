@@ -156,22 +156,27 @@ class GpuRenderer:
                                             _ptr(normal_depth)), "ptg_render_features")
         return albedo, normal_depth
 
+    def _denoise(self, entry, params, inputs, want_bgra, out_radiance):
+        """ptg_denoise or ptg_denoise_guided (`entry`) over `inputs`, device
+        float32 [h, w, 4] tensors with the radiance first."""
+        import torch
+        h, w = inputs[0].shape[:2]
+        for t in inputs:
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        if out_radiance is None:
+            out_radiance = torch.empty_like(inputs[0])
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=inputs[0].device) if want_bgra else None
+        N.check(getattr(N.lib(), entry)(self._ctx, w, h, C.byref(params), *map(_ptr, inputs), _ptr(out_radiance), _ptr(bgra)),
+                entry)
+        return out_radiance, bgra
+
     def denoise(self, radiance, albedo, normal_depth, params=None, want_bgra=True, out_radiance=None):
         """ptg_denoise over device float32 [h, w, 4] tensors: (denoised
         radiance, bgra uint8 [h, w, 4] or None).  `out_radiance` may be
         `radiance` itself.  Asynchronous."""
-        import torch
         from .denoise import DenoiseParams
         p = params if params is not None else DenoiseParams.default()
-        h, w = radiance.shape[:2]
-        for t in (radiance, albedo, normal_depth):
-            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
-        if out_radiance is None:
-            out_radiance = torch.empty_like(radiance)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
-        N.check(N.lib().ptg_denoise(self._ctx, w, h, C.byref(p), _ptr(radiance), _ptr(albedo), _ptr(normal_depth),
-                                    _ptr(out_radiance), _ptr(bgra)), "ptg_denoise")
-        return out_radiance, bgra
+        return self._denoise("ptg_denoise", p, (radiance, albedo, normal_depth), want_bgra, out_radiance)
 
     def render_denoised(self, cfg: N.RenderConfig, params=None):
         """render + render_features + denoise of the whole image: (bgra,
@@ -203,18 +208,9 @@ class GpuRenderer:
         """ptg_denoise_guided over device float32 [h, w, 4] tensors: (denoised
         radiance, bgra uint8 [h, w, 4] or None).  `out_radiance` may be
         `radiance` itself.  Asynchronous."""
-        import torch
         from .denoise import DenoiseGuidedParams
         p = params if params is not None else DenoiseGuidedParams.default()
-        h, w = radiance.shape[:2]
-        for t in (radiance, albedo, normal_depth, moments):
-            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
-        if out_radiance is None:
-            out_radiance = torch.empty_like(radiance)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
-        N.check(N.lib().ptg_denoise_guided(self._ctx, w, h, C.byref(p), _ptr(radiance), _ptr(albedo), _ptr(normal_depth),
-                                           _ptr(moments), _ptr(out_radiance), _ptr(bgra)), "ptg_denoise_guided")
-        return out_radiance, bgra
+        return self._denoise("ptg_denoise_guided", p, (radiance, albedo, normal_depth, moments), want_bgra, out_radiance)
 
     def render_denoised_guided(self, cfg: N.RenderConfig, params=None):
         """render_moments + render_features + denoise_guided of the whole

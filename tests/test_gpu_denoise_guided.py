@@ -8,37 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, arrays_copy, scene_for
+from denoise_inputs import guided_inputs as _inputs
 from ptlumi import validator as V
 from ptlumi.denoise import DenoiseGuidedParams, atrous_guided_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(w, h, seed):
-    """Noisy radiance over piecewise-smooth guides (three vertical bands that
-    differ in albedo, normal, depth and noise level), with one NaN and one
-    +inf pixel where the image has room for them; moments whose variance of
-    the mean is drawn per band, with a few negative, NaN and infinite entries."""
-    rng = np.random.default_rng(seed)
-    band = (np.arange(w) * 3 // max(w, 1))[None, :].repeat(h, 0)
-    base_a = np.float32([[0.8, 0.3, 0.2, 1.0], [0.2, 0.5, 0.9, 1.0], [1.0, 1.0, 1.0, 0.0]])
-    base_n = np.float32([[0.0, 0.0, 1.0, 5.0], [0.6, 0.0, 0.8, 9.0], [0.0, 0.0, 0.0, 0.0]])
-    alb = (base_a[band] + rng.normal(0, 0.01, (h, w, 4))).astype(np.float32)
-    nd = (base_n[band] + rng.normal(0, 0.02, (h, w, 4))).astype(np.float32)
-    noise = np.float32([0.2, 0.02, 0.5])[band]
-    light = np.float32([1.0, 0.5, 2.0])[band][..., None] + rng.normal(0, 1, (h, w, 3)) * noise[..., None]
-    rad = np.zeros((h, w, 4), np.float32)
-    rad[..., :3] = (alb[..., :3] * light).astype(np.float32)
-    mom = np.zeros((h, w, 4), np.float32)
-    mom[..., 0] = rad[..., 1]
-    mom[..., 2] = (noise * noise * rng.uniform(0.5, 1.5, (h, w))).astype(np.float32)
-    mom[..., 3] = 16
-    if w * h >= 15:
-        rad[h // 2, w // 3, 1] = np.nan
-        rad[h // 3, (2 * w) // 3, 0] = np.inf
-        flat = mom[..., 2].reshape(-1)
-        flat[1], flat[4], flat[7], flat[10], flat[13] = -0.5, np.nan, np.inf, -np.inf, 0.0
-    return rad, alb, nd, mom
 
 
 def _same_bits(got, want):
