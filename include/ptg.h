@@ -355,6 +355,56 @@ int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoi
                        const ptg_float4* normal_depth, const ptg_float4* moments,
                        ptg_float4* out_radiance, ptg_uchar4* out_bgra);
 
+/* ---- temporal accumulation -----------------------------------------------
+ * Carries last frame's accumulated radiance and luminance moments into this
+ * frame.  Per pixel: the first-hit point (the pixel's centre ray through
+ * `cam`, at the mean first-hit distance normal_depth.w / albedo.w) is
+ * projected into `hist_cam`; of the four bilinear taps around it, those that
+ * lie inside the image, carry a finite radiance, a positive coverage and a
+ * positive sample count, and show the same surface (depth, normal and albedo
+ * within the tolerances below) give the history; it is blended with this
+ * frame's pixel by sample counts, the history's capped at max_history:
+ *   a = n / (min(n_hist, max_history) + n),  out = hist + a * (this - hist)
+ * for the radiance and for the two moments.  A pixel without a valid tap
+ * keeps this frame's bits; a pixel whose own radiance is not finite (or whose
+ * moments hold no sample) and that has a history takes the history alone, so
+ * it comes out finite.  Every operation is one float32 rounding in a fixed
+ * order (DESIGN.md 4.13 is the definition; denoise.temporal_reference the CPU
+ * restatement, bit for bit). */
+typedef struct {
+    float max_history;       /* cap on the history's effective sample count, in samples */
+    float depth_tolerance;   /* relative: |z_hist - z_expected| <= tol * max(z_hist, z_expected) */
+    float normal_tolerance;  /* squared distance of the two normal.xyz */
+    float albedo_tolerance;  /* squared distance of the two (albedo.rgb, coverage) */
+} ptg_temporal_params;
+void ptg_temporal_params_default(ptg_temporal_params* params);
+/* radiance, moments, albedo, normal_depth: this frame's [h][w] ptg_float4
+ * images as ptg_render_moments (out_accum, out_moments) and
+ * ptg_render_features write them; cam: the camera they were rendered with
+ * (for a motion-blurred frame, one of its subframe cameras).  hist_radiance,
+ * hist_moments: the previous call's out_radiance and out_moments;
+ * hist_albedo, hist_normal_depth, hist_cam: the previous frame's guides and
+ * camera.  The images are DEVICE pointers; the two cameras are HOST
+ * pointers, read before the call returns.  hist_cam and the four hist_*
+ * images are all null (first frame: the outputs are the inputs' bits, with
+ * out_radiance.w = 0) or all set; a mix is PTG_E_INVALID.
+ * out_radiance ([h][w], w component 0) and out_moments ([h][w], the layout
+ * of ptg_render_moments: m1, m2, variance of the mean, sample count; it goes
+ * into ptg_denoise_guided and back in as the next frame's hist_moments) may
+ * be this frame's radiance and moments themselves, which are read only at the
+ * pixel written; an output that is one of the hist_* images, which are
+ * gathered from neighbours, is PTG_E_INVALID, as are out_radiance ==
+ * out_moments and a parameter that is not positive and finite.  out_bgra
+ * (optional) is tonemap_pixel of out_radiance.  w or h above 2^24 is
+ * PTG_E_RANGE.  Asynchronous on the context's stream. */
+int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_params* params,
+                            const ptg_camera* cam, const ptg_camera* hist_cam,
+                            const ptg_float4* radiance, const ptg_float4* moments,
+                            const ptg_float4* albedo, const ptg_float4* normal_depth,
+                            const ptg_float4* hist_radiance, const ptg_float4* hist_moments,
+                            const ptg_float4* hist_albedo, const ptg_float4* hist_normal_depth,
+                            ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra);
+
 /* Work counters of the last ptg_render* call (filled only while counting is
  * on, ptg_counters_enable; counting uses a separate, slower build of the
  * kernels):

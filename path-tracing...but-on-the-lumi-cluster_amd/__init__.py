@@ -7,9 +7,12 @@ Python identifier).  Layout:
   csrc/            HIP kernels (csrc/pt_kernels.hip, csrc/device/) and the
                    host C++ scene restatement (csrc/host/) -> _build/libptg.so
   native.py        ctypes binding of include/ptg.h
-  renderer.py      GpuRenderer: upload + render through the C ABI
-  denoise.py       DenoiseParams and atrous_reference, the CPU restatement of
-                   ptg_denoise (NumPy float32 + the C library's exp)
+  renderer.py      GpuRenderer: upload + render through the C ABI;
+                   TemporalDenoiser: a frame sequence through the temporal
+                   accumulation and the variance-guided filter
+  denoise.py       the parameter structures and the CPU restatements of
+                   ptg_denoise, ptg_denoise_guided and ptg_temporal_accumulate
+                   (NumPy float32 + the C library's exp)
   distributed.py   one process per GPU: tile / frame sharding, RCCL gather
   validator.py     validator.py-equivalent PSNR check (numpy)
   assets.py        scene asset preparation (reference OBJs + substitutes)
@@ -18,11 +21,11 @@ Python identifier).  Layout:
 from . import assets, native, validator  # noqa: F401
 from .native import RenderConfig, Scene, write_bmp  # noqa: F401
 
-__all__ = ["assets", "native", "validator", "RenderConfig", "Scene", "write_bmp", "GpuRenderer"]
+__all__ = ["assets", "native", "validator", "RenderConfig", "Scene", "write_bmp", "GpuRenderer", "TemporalDenoiser"]
 
 
 def __getattr__(name):
-    if name == "GpuRenderer":
-        from .renderer import GpuRenderer
-        return GpuRenderer
+    if name in ("GpuRenderer", "TemporalDenoiser"):
+        from . import renderer
+        return getattr(renderer, name)
     raise AttributeError(name)

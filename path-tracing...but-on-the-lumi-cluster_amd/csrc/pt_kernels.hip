@@ -15,6 +15,8 @@
 //   k_dn_demodulate<GUIDED>, k_dn_atrous<STEP>, k_dn_remodulate
 //                   the a-trous denoisers: STEP is DenoiseStep (fixed sigmas)
 //                   or DenoiseGuidedStep (variance-guided)
+//   k_temporal_accumulate  last frame's radiance and moments, reprojected
+//                   and blended with this frame's by sample count
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
@@ -1107,6 +1109,142 @@ __global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, 
     const f3 c = V3(v.x * dn_floor(a.x, fl), v.y * dn_floor(a.y, fl), v.z * dn_floor(a.z, fl));
     out[i] = make_float4(c.x, c.y, c.z, 0.0f);
     if(out_bgra) out_bgra[i] = tonemap(c);
+}
+
+// ---- temporal accumulation ----
+
+// The parts of a ptg_camera the reprojection reads.
+struct TemporalCam {
+    m3 ori;
+    f3 pos;
+    float aspect, ifl, fd;
+};
+struct TemporalArgs {
+    uint32_t w, h;
+    uint32_t has_history;                  // 0: first frame, the hist_* pointers are null
+    float max_history, depth_tolerance, normal_tolerance, albedo_tolerance;
+    TemporalCam cam, hist;
+};
+
+// the variance of the mean of n samples with the moments (m1, m2), as k_accumulate ends
+__device__ __forceinline__ float tp_var_of_mean(float m1, float m2, float n)
+{
+    const float dvar = m2 - m1 * m1;
+    const float var = dvar > 0.0f ? dvar : 0.0f;
+    return n >= 2.0f ? var / (n - 1.0f) : 0.0f;
+}
+
+// One work-item per pixel: the pixel's first-hit point, from its centre ray
+// through `cam` and its mean depth, is projected into `hist`; the four
+// bilinear taps around it that show the same surface (depth, normal, albedo)
+// give the history's radiance and moments, which are blended with this
+// frame's by their sample counts.  Every operation is one float32 rounding in
+// the order DESIGN.md gives.  This frame's images are read at the pixel alone
+// (the outputs may be the radiance and moments themselves: no __restrict__
+// on those four); the history is gathered.
+__global__ __launch_bounds__(kBlock) void k_temporal_accumulate(TemporalArgs a, const float4* radiance, const float4* moments,
+                                                                const float4* __restrict__ albedo,
+                                                                const float4* __restrict__ normal_depth,
+                                                                const float4* __restrict__ hist_radiance,
+                                                                const float4* __restrict__ hist_moments,
+                                                                const float4* __restrict__ hist_albedo,
+                                                                const float4* __restrict__ hist_normal_depth,
+                                                                float4* out_radiance, float4* out_moments,
+                                                                uchar4* __restrict__ out_bgra)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= a.w * a.h) return;
+    const uint32_t x = i % a.w, y = i / a.w;
+    const float4 R = radiance[i], M = moments[i], A = albedo[i], G = normal_depth[i];
+    float sw = 0.0f, scx = 0.0f, scy = 0.0f, scz = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
+    const float cov = A.w;
+    if(a.has_history && cov > 0.0f)
+    {
+        const float z = G.w / cov;
+        const float uvx = (((float)x + 0.5f) / (float)a.w * 2.0f - 1.0f) * a.cam.aspect;
+        const float uvy = -(((float)y + 0.5f) / (float)a.h * 2.0f - 1.0f);
+        const f3 d = normalize(V3(uvx * a.cam.ifl * a.cam.fd, uvy * a.cam.ifl * a.cam.fd, -1.0f * a.cam.fd));
+        const f3 dir = mul_m3v3(a.cam.ori, d);
+        const f3 P = a.cam.pos + dir * z;
+        const f3 q = P - a.hist.pos;
+        const f3 l = mul_v3m3(q, a.hist.ori);
+        if(l.z < 0.0f)
+        {
+            const float t = -l.z;
+            const float sx = (l.x / t) / a.hist.ifl / a.hist.aspect;
+            const float sy = -((l.y / t) / a.hist.ifl);
+            const float fx = (sx + 1.0f) * 0.5f * (float)a.w - 0.5f;
+            const float fy = (sy + 1.0f) * 0.5f * (float)a.h - 0.5f;
+            const float ze = fsqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
+            if(__builtin_isfinite(fx) && __builtin_isfinite(fy))
+            {
+                const float ix = floorf(fx), iy = floorf(fy);
+                const float tx = fx - ix, ty = fy - iy;
+                const float xmax = (float)(a.w - 1u), ymax = (float)(a.h - 1u);
+#pragma unroll
+                for(int b = 0; b < 2; ++b)
+                {
+                    const float Y = iy + (float)b;
+                    const float wy = b ? ty : 1.0f - ty;
+#pragma unroll
+                    for(int c = 0; c < 2; ++c)
+                    {
+                        const float X = ix + (float)c;
+                        const float bw = (c ? tx : 1.0f - tx) * wy;
+                        // inside on the floats; an integer only after that
+                        if(!(X >= 0.0f && X <= xmax && Y >= 0.0f && Y <= ymax)) continue;
+                        const size_t t4 = size_t((uint32_t)Y) * a.w + size_t((uint32_t)X);
+                        const float4 HA = hist_albedo[t4];
+                        if(!(HA.w > 0.0f)) continue;
+                        const float4 H = hist_radiance[t4];
+                        if(!finite3(V3(H.x, H.y, H.z))) continue;
+                        const float4 HM = hist_moments[t4];
+                        if(!(HM.w > 0.0f)) continue;
+                        const float4 HG = hist_normal_depth[t4];
+                        const float zh = HG.w / HA.w;
+                        const float zm = zh > ze ? zh : ze;
+                        if(!(fabsf(zh - ze) <= a.depth_tolerance * zm)) continue;
+                        const float nx = G.x - HG.x, ny = G.y - HG.y, nz = G.z - HG.z;
+                        const float dn = (nx * nx + ny * ny) + nz * nz;
+                        if(!(dn <= a.normal_tolerance)) continue;
+                        const float ax = A.x - HA.x, ay = A.y - HA.y, az = A.z - HA.z, aw = A.w - HA.w;
+                        const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
+                        if(!(da <= a.albedo_tolerance)) continue;
+                        sw = sw + bw;
+                        scx = scx + bw * H.x;
+                        scy = scy + bw * H.y;
+                        scz = scz + bw * H.z;
+                        s1 = s1 + bw * HM.x;
+                        s2 = s2 + bw * HM.y;
+                        sn = sn + bw * HM.w;
+                    }
+                }
+            }
+        }
+    }
+    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
+    if(sw > 0.0f)
+    {
+        const float hx = scx / sw, hy = scy / sw, hz = scz / sw;
+        const float h1 = s1 / sw, h2 = s2 / sw, hn = sn / sw;
+        const float nh = hn < a.max_history ? hn : a.max_history;
+        if(finite3(V3(R.x, R.y, R.z)) && M.w > 0.0f)
+        {
+            const float nt = nh + M.w;
+            const float al = M.w / nt;
+            oc = make_float4(hx + al * (R.x - hx), hy + al * (R.y - hy), hz + al * (R.z - hz), 0.0f);
+            const float m1 = h1 + al * (M.x - h1), m2 = h2 + al * (M.y - h2);
+            om = make_float4(m1, m2, tp_var_of_mean(m1, m2, nt), nt);
+        }
+        else
+        {   // nothing usable in this frame: the history alone
+            oc = make_float4(hx, hy, hz, 0.0f);
+            om = make_float4(h1, h2, tp_var_of_mean(h1, h2, nh), nh);
+        }
+    }
+    out_radiance[i] = oc;
+    out_moments[i] = om;
+    if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
 }
 
 // ---------------------------------------------------------------- runtime --
@@ -2325,6 +2463,68 @@ int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoi
     };
     return denoise_passes(ctx, w, h, P.iterations, P.albedo_floor, step_of, radiance, albedo, normal_depth, moments, out_radiance,
                           out_bgra);
+}
+
+void ptg_temporal_params_default(ptg_temporal_params* p)
+{
+    if(!p) return;
+    // the best row of tools/denoise_study.py --temporal --sweep (profiles/denoise_study/temporal_study.json)
+    p->max_history = 128.0f;
+    p->depth_tolerance = 0.02f;
+    p->normal_tolerance = 0.1f;
+    p->albedo_tolerance = 0.25f;
+}
+
+int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_params* params,
+                            const ptg_camera* cam, const ptg_camera* hist_cam, const ptg_float4* radiance,
+                            const ptg_float4* moments, const ptg_float4* albedo, const ptg_float4* normal_depth,
+                            const ptg_float4* hist_radiance, const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
+                            const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments,
+                            ptg_uchar4* out_bgra)
+{
+    if(int r = bind(ctx)) return r;
+    if(!params || !cam || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
+        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: null argument");
+    const ptg_temporal_params P = *params;
+    for(float s: {P.max_history, P.depth_tolerance, P.normal_tolerance, P.albedo_tolerance})
+        if(!(s > 0.0f) || !std::isfinite(s))
+            return fail(PTG_E_INVALID, "ptg_temporal_accumulate: max_history and the tolerances must be positive and finite");
+    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
+    int given = hist_cam ? 1 : 0;
+    for(const void* p: hist) given += p ? 1 : 0;
+    if(given != 0 && given != 5)
+        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: hist_cam and the four hist_* images are all null or all set");
+    if(static_cast<void*>(out_radiance) == static_cast<void*>(out_moments))
+        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: out_radiance and out_moments are one buffer");
+    for(const void* p: hist)
+        if(p && (p == out_radiance || p == out_moments))
+            return fail(PTG_E_INVALID, "ptg_temporal_accumulate: an output is a hist_* image (the history is gathered from neighbours)");
+    if(uint64_t(w) * h == 0) return PTG_OK;
+    // pixel coordinates are compared as floats: exact below 2^24
+    if(uint64_t(w) * h >= (1ull << 31) || w > (1u << 24) || h > (1u << 24)) return fail(PTG_E_RANGE, "image too large");
+    const auto cam_of = [](const ptg_camera& c) {
+        TemporalCam t;
+        for(int k = 0; k < 3; ++k) t.ori.r[k] = f3{c.orientation.r[k].x, c.orientation.r[k].y, c.orientation.r[k].z};
+        t.pos = f3{c.position.x, c.position.y, c.position.z};
+        t.aspect = c.aspect_ratio;
+        t.ifl = c.inv_focal_length;
+        t.fd = c.focal_distance;
+        return t;
+    };
+    TemporalArgs a;
+    a.w = w; a.h = h;
+    a.has_history = given ? 1u : 0u;
+    a.max_history = P.max_history;
+    a.depth_tolerance = P.depth_tolerance;
+    a.normal_tolerance = P.normal_tolerance;
+    a.albedo_tolerance = P.albedo_tolerance;
+    a.cam = cam_of(*cam);
+    a.hist = cam_of(given ? *hist_cam : *cam);
+    const auto in = [](const ptg_float4* p) { return reinterpret_cast<const float4*>(p); };
+    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate, a, in(radiance), in(moments), in(albedo),
+                        in(normal_depth), in(hist_radiance), in(hist_moments), in(hist_albedo), in(hist_normal_depth),
+                        reinterpret_cast<float4*>(out_radiance), reinterpret_cast<float4*>(out_moments),
+                        reinterpret_cast<uchar4*>(out_bgra));
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

@@ -7,6 +7,11 @@ rounding, in the order the definition gives, and the weight's ``exp`` is the C
 library's double ``exp`` called once per tap (``math.exp``; NumPy's vectorised
 ``exp`` is a different algorithm).  On a glibc host it gives the bits the GPU
 kernels give; it is the documented CPU route and the tests' checker.
+
+Further down: the sample moments and the variance-guided filter
+(``moments_reference``, ``atrous_guided_reference``), and the temporal
+accumulation (``TemporalParams``, ``temporal_reference``: the restatement of
+``ptg_temporal_accumulate``).
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ MAX_ITERATIONS = 8
 
 
 class _Params:
-    """What the two parameter structures share; each names the library's
+    """What the parameter structures share; each names the library's
     default function and its fields that must be positive and finite."""
 
     @classmethod
@@ -39,7 +44,7 @@ class _Params:
         return {k: getattr(self, k) for k, _ in self._fields_}
 
     def validate(self):
-        if self.iterations > MAX_ITERATIONS:
+        if getattr(self, "iterations", 0) > MAX_ITERATIONS:
             raise ValueError("iterations > %d" % MAX_ITERATIONS)
         for k in self._positive:
             v = getattr(self, k)
@@ -244,3 +249,146 @@ def atrous_guided_reference(radiance, albedo, normal_depth, moments, params: Den
         out[..., :3] = I * m                                       # remodulate
     assert out.dtype == f32
     return out
+
+
+# ---- temporal accumulation ------------------------------------------------------
+
+
+class TemporalParams(_Params, C.Structure):
+    """ptg_temporal_params.  ``TemporalParams.default()`` asks the library."""
+    _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float),
+                ("albedo_tolerance", C.c_float)]
+    _default_fn = "ptg_temporal_params_default"
+    _positive = ("max_history", "depth_tolerance", "normal_tolerance", "albedo_tolerance")
+
+
+def _camera_parts(cam):
+    """(orientation rows [3][3], position [3], aspect_ratio, inv_focal_length,
+    focal_distance) as float32 of a CAMERA_DTYPE record or a ctypes ptg_camera."""
+    f32 = np.float32
+    if isinstance(cam, C.Structure):
+        cam = np.frombuffer(bytes(cam), dtype=N.CAMERA_DTYPE, count=1)[0]
+    cam = np.asarray(cam, dtype=N.CAMERA_DTYPE).reshape(())
+    ori = np.array(cam["orientation"], f32)[:, :3]
+    pos = np.array(cam["position"], f32)[:3]
+    return ori, pos, f32(cam["aspect_ratio"]), f32(cam["inv_focal_length"]), f32(cam["focal_distance"])
+
+
+def _dot3(ax, ay, az, bx, by, bz):
+    """The device's dot: (a.x * b.x + a.y * b.y) + a.z * b.z."""
+    return (ax * bx + ay * by) + az * bz
+
+
+def _var_of_mean(m1, m2, n):
+    """(max(m2 - m1 * m1, 0) / (n - 1), 0 when n < 2), as moments_reference ends."""
+    f32 = np.float32
+    d = m2 - m1 * m1
+    var = np.where(d > 0, d, f32(0))
+    return np.where(n >= 2, var / (n - f32(1)), f32(0)).astype(f32)
+
+
+def temporal_reference(cam, hist_cam, radiance, moments, albedo, normal_depth, hist_radiance=None, hist_moments=None,
+                       hist_albedo=None, hist_normal_depth=None, params: TemporalParams = None, found=None):
+    """ptg_temporal_accumulate on the CPU: [h, w, 4] float32 arrays in,
+    (out_radiance, out_moments) out.  `cam` / `hist_cam` are CAMERA_DTYPE
+    records or ctypes ptg_camera structures; `hist_cam` and the four hist_*
+    arrays are all None (first frame) or all given.  A bool [h, w] array
+    passed as `found` is set where a pixel found history."""
+    P = params if params is not None else TemporalParams.default()
+    P.validate()
+    f32 = np.float32
+    R, M, A, G = (np.ascontiguousarray(a, dtype=f32) for a in (radiance, moments, albedo, normal_depth))
+    h, w = R.shape[:2]
+    assert R.shape == M.shape == A.shape == G.shape == (h, w, 4)
+    hist = (hist_cam, hist_radiance, hist_moments, hist_albedo, hist_normal_depth)
+    given = sum(a is not None for a in hist)
+    if given not in (0, 5):
+        raise ValueError("hist_cam and the four hist_* images are all None or all given")
+    out_c = R.copy()
+    out_c[..., 3] = 0
+    out_m = M.copy()
+    if found is not None:
+        found[...] = False
+    if not given or w * h == 0:
+        return out_c, out_m
+    H, HM, HA, HG = (np.ascontiguousarray(a, dtype=f32) for a in hist[1:])
+    assert H.shape == HM.shape == HA.shape == HG.shape == (h, w, 4)
+    ori, pos, aspect, ifl, fd = _camera_parts(cam)
+    hori, hpos, haspect, hifl, _ = _camera_parts(hist_cam)
+    mh, tz, tn, ta = f32(P.max_history), f32(P.depth_tolerance), f32(P.normal_tolerance), f32(P.albedo_tolerance)
+    wf, hf = f32(w), f32(h)
+    with np.errstate(all="ignore"):
+        # 1-2: the pixel's first-hit point
+        cov = A[..., 3]
+        ok = cov > 0
+        z = G[..., 3] / cov
+        xs = np.arange(w, dtype=f32)[None, :].repeat(h, 0)
+        ys = np.arange(h, dtype=f32)[:, None].repeat(w, 1)
+        uvx = ((xs + f32(0.5)) / wf * f32(2) - f32(1)) * aspect
+        uvy = -((ys + f32(0.5)) / hf * f32(2) - f32(1))
+        dx, dy, dz = uvx * ifl * fd, uvy * ifl * fd, np.full((h, w), f32(-1) * fd, f32)
+        ln = np.sqrt(_dot3(dx, dy, dz, dx, dy, dz))
+        dx, dy, dz = dx / ln, dy / ln, dz / ln
+        # mul_m3v3(ori, d): component c is the dot of (r0.c, r1.c, r2.c) with d
+        dirv = [_dot3(ori[0, c], ori[1, c], ori[2, c], dx, dy, dz) for c in range(3)]
+        Pw = [pos[c] + dirv[c] * z for c in range(3)]
+        # 3: into the history camera
+        q = [Pw[c] - hpos[c] for c in range(3)]
+        l = [_dot3(hori[r, 0], hori[r, 1], hori[r, 2], q[0], q[1], q[2]) for r in range(3)]   # mul_v3m3(q, ori)
+        ok &= l[2] < 0
+        t = -l[2]
+        sx = (l[0] / t) / hifl / haspect
+        sy = -((l[1] / t) / hifl)
+        fx = (sx + f32(1)) * f32(0.5) * wf - f32(0.5)
+        fy = (sy + f32(1)) * f32(0.5) * hf - f32(0.5)
+        ze = np.sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2])
+        ok &= np.isfinite(fx) & np.isfinite(fy)
+        # 4: the bilinear taps, b (rows) outer and a (columns) inner
+        ix, iy = np.floor(fx), np.floor(fy)
+        tx, ty = fx - ix, fy - iy
+        sw = np.zeros((h, w), f32)
+        sc = np.zeros((h, w, 3), f32)
+        s1, s2, sn = np.zeros((h, w), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
+        for b in (0, 1):
+            Y = iy + f32(b)
+            wy = ty if b else f32(1) - ty
+            for a in (0, 1):
+                X = ix + f32(a)
+                bw = (tx if a else f32(1) - tx) * wy
+                v = ok & (X >= 0) & (X <= f32(w - 1)) & (Y >= 0) & (Y <= f32(h - 1))
+                xi = np.where(v, X, f32(0)).astype(np.int64)
+                yi = np.where(v, Y, f32(0)).astype(np.int64)
+                Hq, HMq, HAq, HGq = H[yi, xi], HM[yi, xi], HA[yi, xi], HG[yi, xi]
+                v &= HAq[..., 3] > 0
+                v &= np.isfinite(Hq[..., :3]).all(-1)
+                v &= HMq[..., 3] > 0
+                zh = HGq[..., 3] / HAq[..., 3]
+                v &= np.abs(zh - ze) <= tz * np.where(zh > ze, zh, ze)
+                v &= _sq3(G[..., :3] - HGq[..., :3]) <= tn
+                d = A - HAq
+                v &= (_sq3(d) + d[..., 3] * d[..., 3]) <= ta
+                sw = np.where(v, sw + bw, sw)
+                sc = np.where(v[..., None], sc + bw[..., None] * Hq[..., :3], sc)
+                s1 = np.where(v, s1 + bw * HMq[..., 0], s1)
+                s2 = np.where(v, s2 + bw * HMq[..., 1], s2)
+                sn = np.where(v, sn + bw * HMq[..., 3], sn)
+        some = sw > 0
+        Hc = sc / sw[..., None]
+        h1, h2, hn = s1 / sw, s2 / sw, sn / sw
+        # 5-7: the blend
+        nh = np.where(hn < mh, hn, mh)
+        nc = M[..., 3]
+        both = some & np.isfinite(R[..., :3]).all(-1) & (nc > 0)
+        nt = nh + nc
+        al = nc / nt
+        c6 = Hc + al[..., None] * (R[..., :3] - Hc)
+        m1 = h1 + al * (M[..., 0] - h1)
+        m2 = h2 + al * (M[..., 1] - h2)
+        mom6 = np.stack([m1, m2, _var_of_mean(m1, m2, nt), nt], -1)
+        mom7 = np.stack([h1, h2, _var_of_mean(h1, h2, nh), nh], -1)
+        out_c[..., :3] = np.where(both[..., None], c6, np.where(some[..., None], Hc, R[..., :3]))
+        out_m = np.where(both[..., None], mom6, np.where(some[..., None], mom7, M))
+    if found is not None:
+        found[...] = some
+    assert out_c.dtype == f32 and out_m.dtype == f32
+    return out_c, np.ascontiguousarray(out_m)

@@ -45,6 +45,20 @@ class SceneView(C.Structure):
                 ("static_instance_count", C.c_size_t), ("subframes", C.c_void_p), ("subframe_count", C.c_size_t)]
 
 
+class Camera(C.Structure):
+    """ptg_camera (96 B; CAMERA_DTYPE is the same bytes as a numpy record)."""
+    _fields_ = [("orientation", C.c_float * 12), ("position", C.c_float * 4), ("aspect_ratio", C.c_float),
+                ("inv_focal_length", C.c_float), ("focal_distance", C.c_float), ("aperture_angle", C.c_float),
+                ("aperture_polygon", C.c_int32), ("aperture_radius", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+    @classmethod
+    def of(cls, cam):
+        """A copy of `cam`: a Camera or a CAMERA_DTYPE record (e.g. Scene.view()["subframes"][k]["cam"])."""
+        if isinstance(cam, cls):
+            return cls.from_buffer_copy(bytes(cam))
+        return cls.from_buffer_copy(np.asarray(cam, dtype=CAMERA_DTYPE).tobytes())
+
+
 class Mesh(C.Structure):
     _fields_ = [("vertex_count", C.c_uint32), ("triangle_count", C.c_uint32), ("index_offset", C.c_uint32),
                 ("base_vertex_offset", C.c_uint32)]
@@ -67,6 +81,7 @@ LIGHT_DTYPE = np.dtype([("direction", "<f4", 4), ("color", "<f4", 4), ("cos_soli
 SUBFRAME_DTYPE = np.dtype([("tlas", "<u4", 2), ("_pad", "<u4", 2), ("cam", CAMERA_DTYPE), ("light", LIGHT_DTYPE)])
 assert NODE_DTYPE.itemsize == 24 and INSTANCE_DTYPE.itemsize == 160
 assert CAMERA_DTYPE.itemsize == 96 and LIGHT_DTYPE.itemsize == 48 and SUBFRAME_DTYPE.itemsize == 160
+assert C.sizeof(Camera) == CAMERA_DTYPE.itemsize
 
 _lib = None
 
@@ -124,6 +139,8 @@ def lib():
         "ptg_render_moments": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P]),
         "ptg_denoise_guided_params_default": (None, [P]),
         "ptg_denoise_guided": (I, [P, U32, U32, P, P, P, P, P, P, P]),
+        "ptg_temporal_params_default": (None, [P]),
+        "ptg_temporal_accumulate": (I, [P, U32, U32, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
         "ptg_counters_enable": (I, [P, I]),
         "ptg_last_counters": (I, [P, P]),
         "ptg_timing_enable": (I, [P, I]),

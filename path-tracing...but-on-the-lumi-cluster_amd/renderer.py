@@ -220,6 +220,38 @@ class GpuRenderer:
         out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
+    # -- temporal accumulation -------------------------------------------------
+    def temporal_accumulate(self, cam, radiance, moments, albedo, normal_depth, history=None, params=None,
+                            want_bgra=False, out_radiance=None, out_moments=None):
+        """ptg_temporal_accumulate over device float32 [h, w, 4] tensors:
+        (accumulated radiance, accumulated moments, bgra uint8 [h, w, 4] or
+        None).  `cam` is this frame's camera (a native.Camera or a
+        CAMERA_DTYPE record); `history` is None (first frame) or (hist_cam,
+        hist_radiance, hist_moments, hist_albedo, hist_normal_depth): the
+        previous frame's camera, the previous call's two outputs and the
+        previous frame's guides.  `out_radiance` / `out_moments` may be
+        `radiance` / `moments` themselves, never a history tensor.
+        Asynchronous."""
+        import torch
+        from .denoise import TemporalParams
+        p = params if params is not None else TemporalParams.default()
+        images = (radiance, moments, albedo, normal_depth) + (tuple(history[1:]) if history is not None else ())
+        h, w = radiance.shape[:2]
+        for t in images:
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        c = N.Camera.of(cam)
+        hc = N.Camera.of(history[0]) if history is not None else None
+        if out_radiance is None:
+            out_radiance = torch.empty_like(radiance)
+        if out_moments is None:
+            out_moments = torch.empty_like(moments)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
+        hist = images[4:] if history is not None else (None,) * 4
+        N.check(N.lib().ptg_temporal_accumulate(self._ctx, w, h, C.byref(p), C.byref(c), C.byref(hc) if hc is not None else None,
+                                                *map(_ptr, images[:4]), *map(_ptr, hist), _ptr(out_radiance),
+                                                _ptr(out_moments), _ptr(bgra)), "ptg_temporal_accumulate")
+        return out_radiance, out_moments, bgra
+
     def tonemap_device(self, colors, out_bgra):
         """tonemap_pixel over a device float32 [..., 4] tensor into a device
         uint8 [..., 4] tensor (ptg_tonemap_device; asynchronous)."""
@@ -338,3 +370,63 @@ class GpuRenderer:
             self.close()
         except Exception:
             pass
+
+
+class TemporalDenoiser:
+    """A frame sequence through the temporal accumulation and the
+    variance-guided filter.  ``step(scene)`` takes a host Scene set to the next
+    frame and does, in order: upload, render_moments, render_features,
+    temporal_accumulate against the state kept from the previous step,
+    denoise_guided of the accumulated radiance with the accumulated moments;
+    it returns (bgra, denoised radiance).  The camera of the reprojection is
+    that of subframe ``subframe_count // 2``, the middle of the frame's
+    motion blur.  Kept for the next step: the accumulated radiance and
+    moments, unfiltered (the filter runs on the output for display only, so
+    the history carries no spatial blur), this frame's guides and that
+    camera.  ``reset()`` drops them: the next step is a first frame.
+
+    ``seed_stride``: path_trace_pixel seeds a sample with (x, y,
+    sample_index, student_id) and not with the frame, so two frames draw the
+    same random numbers per pixel and their noise is correlated wherever the
+    camera barely moves; accumulating such frames gains little and the
+    accumulated variance understates what is left.  Step k of the sequence
+    (counted from the construction or the last reset) therefore renders with
+    ``student_id + k * seed_stride`` in uint32 arithmetic; frame 0 of a
+    sequence has the reference's bits either way, and ``seed_stride=0`` keeps
+    the reference's seeds on every frame."""
+
+    def __init__(self, renderer: GpuRenderer, cfg: N.RenderConfig, temporal_params=None, guided_params=None,
+                 seed_stride=1):
+        self.renderer = renderer
+        self.cfg = cfg
+        self.temporal_params = temporal_params
+        self.guided_params = guided_params
+        self.seed_stride = int(seed_stride)
+        self.reset()
+
+    def reset(self):
+        self.history = None                # (camera, radiance, moments, albedo, normal_depth) of the last step
+        self.frames = 0
+
+    def frame_config(self):
+        """The configuration the next step renders with."""
+        c = self.cfg
+        return N.RenderConfig(c.width, c.height, c.samples_per_pixel, c.max_bounces,
+                              (c.student_id + self.frames * self.seed_stride) & 0xFFFFFFFF,
+                              c.samples_per_motion_blur_step)
+
+    def step(self, scene: N.Scene):
+        r = self.renderer
+        cfg = self.frame_config()
+        r.upload(scene)
+        subframes = scene.view()["subframes"]
+        cam = N.Camera.of(subframes[len(subframes) // 2]["cam"])
+        _, acc, moments = r.render_moments(cfg, want_accum=True)
+        albedo, normal_depth = r.render_features(cfg)
+        # in place: this frame's radiance and moments become the accumulated ones
+        acc, moments, _ = r.temporal_accumulate(cam, acc, moments, albedo, normal_depth, self.history, self.temporal_params,
+                                                out_radiance=acc, out_moments=moments)
+        out, bgra = r.denoise_guided(acc, albedo, normal_depth, moments, self.guided_params, want_bgra=True)
+        self.history = (cam, acc, moments, albedo, normal_depth)
+        self.frames += 1
+        return bgra, out

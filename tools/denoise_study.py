@@ -20,13 +20,28 @@ and 256 spp - one setting has to hold across sample counts - and uses the best
 row; the library's defaults (ptg_denoise_guided_params_default) are the best
 row of the recorded sweep.  Writes <out>/guided_study.json.
 
-Usage: python tools/denoise_study.py [--guided] [--sweep] [--out profiles/<name>]
+--temporal studies the temporal accumulation (ptg_temporal_accumulate through
+TemporalDenoiser): for frames 0 and 450 at 8 .. 64 spp, sequences of 1, 2, 4
+and 8 preceding frames with seed_stride 0 and 1; per row the raw, the
+single-frame guided, the accumulated ("temporal only") and the accumulated +
+guided PSNR of the target frame, the share of its pixels that found history
+and the kernel's time.  Frame 0 has no preceding frames: its sequences are
+frames N .. 1 played backwards, the same camera path in the other direction.
+With --sweep it first ranks a grid of ptg_temporal_params times the
+sigma_luminance of the guided filter that follows by the mean accumulated +
+guided PSNR over both frames at 16 and 64 spp after 4 preceding frames
+(seed_stride 1) and uses the best row; the library's defaults
+(ptg_temporal_params_default) are the best row of the recorded sweep.  Writes
+<out>/temporal_study.json.
+
+Usage: python tools/denoise_study.py [--guided | --temporal] [--sweep] [--out profiles/<name>]
 Writes <out>/denoise_study.json.
 """
 import argparse
 import itertools
 import json
 import os
+import re
 import sys
 import time
 
@@ -38,7 +53,7 @@ import ptlumi_loader  # noqa: E402
 
 P = ptlumi_loader.load()
 N, V = P.native, P.validator
-from ptlumi.denoise import DenoiseGuidedParams, DenoiseParams  # noqa: E402
+from ptlumi.denoise import DenoiseGuidedParams, DenoiseParams, TemporalParams  # noqa: E402
 
 ASSETS = os.path.join(ROOT, "assets")
 W, H = 1280, 720
@@ -173,14 +188,190 @@ def guided_study(args):
     print("wrote", os.path.join(args.out, "guided_study.json"))
 
 
+TEMPORAL_SPPS = (8, 16, 32, 64)
+TEMPORAL_PRECEDING = (1, 2, 4, 8)
+TEMPORAL_SWEEP_SPPS = (16, 64)
+TEMPORAL_SWEEP_PRECEDING = 4
+TEMPORAL_GRID = {
+    "max_history": (16.0, 32.0, 64.0, 128.0, 256.0),
+    "depth_tolerance": (0.02, 0.05, 0.1),
+    "normal_tolerance": (0.02, 0.1, 0.5),
+    "albedo_tolerance": (0.01, 0.05, 0.25),
+}
+TEMPORAL_SIGMA_LUMINANCE = (0.5, 1.0, 2.0, 4.0)
+CHECK = {"width": 320, "height": 180, "spp": 16, "reference_spp": 256, "frames": (447, 448, 449, 450)}
+
+
+def sequence(frame, preceding):
+    """The frames of a sequence that ends at `frame`; before frame 0 there is
+    nothing, so its sequences run backwards from frame `preceding`."""
+    if frame >= preceding:
+        return list(range(frame - preceding, frame + 1))
+    return list(range(frame + preceding, frame - 1, -1))
+
+
+def dump_rows_compact(result, path):
+    """json.dump(result, indent=1) with every row of the table and of the
+    sweep on one line: 540 swept rows stay a few hundred lines."""
+    rows = []
+
+    def hold(row):
+        rows.append(json.dumps(row))
+        return "@row%d@" % (len(rows) - 1)
+
+    doc = dict(result, table=[hold(row) for row in result["table"]])
+    if "sweep" in doc:
+        doc["sweep"] = dict(doc["sweep"], rows=[hold(row) for row in doc["sweep"]["rows"]])
+    text = re.sub(r'"@row(\d+)@"', lambda m: rows[int(m.group(1))], json.dumps(doc, indent=1))
+    with open(path, "w") as fh:
+        fh.write(text + "\n")
+
+
+def temporal_study(args):
+    r = P.GpuRenderer(0)
+    result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP, "spps": TEMPORAL_SPPS,
+                         "preceding": TEMPORAL_PRECEDING, "sequences": {str(f): sequence(f, 8) for f in FRAMES}},
+              "device": torch.cuda.get_device_name(0)}
+    cfg = N.RenderConfig.make(W, H, REF_SPP)
+    scene = N.Scene(ASSETS, cfg)
+    ref_half = {}
+    for f in FRAMES:
+        scene.setup_frame(f)
+        r.upload(scene)
+        bgra, _ = r.render(cfg)
+        r.synchronize()
+        ref_half[f] = V.downscale_half(V.bgra_to_rgb(bgra.cpu().numpy()))
+    scene.close()
+
+    def tonemapped(radiance):
+        return r.tonemap_device(radiance, torch.empty(radiance.shape, dtype=torch.uint8, device=radiance.device))
+
+    def frames_of(scene, cfg, frames, seed_stride):
+        """Per frame of the sequence what TemporalDenoiser.step renders: (camera, radiance, moments, albedo, normal_depth)."""
+        td = P.TemporalDenoiser(r, cfg, seed_stride=seed_stride)
+        out = []
+        for f in frames:
+            scene.setup_frame(f)
+            r.upload(scene)
+            sub = scene.view()["subframes"]
+            c = td.frame_config()
+            _, acc, mom = r.render_moments(c, want_accum=True)
+            out.append((N.Camera.of(sub[len(sub) // 2]["cam"]), acc, mom) + r.render_features(c))
+            td.frames += 1
+        return out
+
+    def accumulate(steps, tp):
+        """The sequence through ptg_temporal_accumulate, as TemporalDenoiser.step chains it (not in place)."""
+        hist = None
+        for cam, acc, mom, alb, nd in steps:
+            rad, m, _ = r.temporal_accumulate(cam, acc, mom, alb, nd, hist, tp)
+            hist = (cam, rad, m, alb, nd)
+        return hist
+
+    tparams, gparams = TemporalParams.default(), DenoiseGuidedParams.default()
+    if args.sweep:
+        held = {}
+        for spp in TEMPORAL_SWEEP_SPPS:
+            cfg = N.RenderConfig.make(W, H, spp)
+            scene = N.Scene(ASSETS, cfg)
+            for f in FRAMES:
+                held[spp, f] = frames_of(scene, cfg, sequence(f, TEMPORAL_SWEEP_PRECEDING), 1)
+            scene.close()
+        # beside the ranking, the suite's end-to-end check of every row (not ranked on)
+        c = CHECK
+        cfg = N.RenderConfig.make(c["width"], c["height"], c["reference_spp"])
+        scene = N.Scene(ASSETS, cfg)
+        scene.setup_frame(c["frames"][-1])
+        r.upload(scene)
+        bgra, _ = r.render(cfg)
+        r.synchronize()
+        check_ref = V.bgra_to_rgb(bgra.cpu().numpy())
+        scene.close()
+        cfg = N.RenderConfig.make(c["width"], c["height"], c["spp"])
+        scene = N.Scene(ASSETS, cfg)
+        check_steps = frames_of(scene, cfg, c["frames"], 1)
+        r.upload(scene)
+        single, _ = r.render_denoised_guided(cfg)
+        check_single = float(V.psnr(check_ref, V.bgra_to_rgb(single.cpu().numpy())))
+        scene.close()
+        rows = []
+        keys = list(TEMPORAL_GRID)
+        for combo in itertools.product(*(TEMPORAL_GRID[k] for k in keys)):
+            tp = TemporalParams.default(**dict(zip(keys, combo)))
+            acc = {cell: accumulate(steps, tp) for cell, steps in held.items()}
+            chk = accumulate(check_steps, tp)
+            only = {"%d@%d" % (f, spp): psnr_half(ref_half[f], tonemapped(h[1])) for (spp, f), h in acc.items()}
+            for sl in TEMPORAL_SIGMA_LUMINANCE:
+                gp = DenoiseGuidedParams.default(sigma_luminance=sl)
+                ps = {}
+                for (spp, f), h in acc.items():
+                    _, bgra = r.denoise_guided(h[1], h[3], h[4], h[2], gp)
+                    ps["%d@%d" % (f, spp)] = psnr_half(ref_half[f], bgra)
+                _, bgra = r.denoise_guided(chk[1], chk[3], chk[4], chk[2], gp)
+                rows.append(dict(zip(keys, combo), sigma_luminance=sl, psnr=ps, mean=float(np.mean(list(ps.values()))),
+                                 temporal_only=only, temporal_only_mean=float(np.mean(list(only.values()))),
+                                 check_frame450=float(V.psnr(check_ref, V.bgra_to_rgb(bgra.cpu().numpy())))))
+            if len(rows) % 40 == 0:
+                print("sweep: %d rows" % len(rows), flush=True)
+        rows.sort(key=lambda x: -x["mean"])
+        best = rows[0]
+        tparams = TemporalParams.default(**{k: best[k] for k in keys})
+        gparams = DenoiseGuidedParams.default(sigma_luminance=best["sigma_luminance"])
+        result["sweep"] = {"spps": TEMPORAL_SWEEP_SPPS, "preceding": TEMPORAL_SWEEP_PRECEDING, "seed_stride": 1,
+                           "grid": TEMPORAL_GRID, "sigma_luminance": TEMPORAL_SIGMA_LUMINANCE, "check": CHECK,
+                           "check_single_frame_guided": check_single, "best": best, "rows": rows}
+        print("sweep: best", best, "single-frame guided check", check_single, flush=True)
+        del held, acc
+    result["params"] = tparams.as_dict()
+    result["guided_params"] = gparams.as_dict()
+    result["library_guided_params"] = DenoiseGuidedParams.default().as_dict()
+
+    table = []
+    for spp in TEMPORAL_SPPS:
+        cfg = N.RenderConfig.make(W, H, spp)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene)
+            raw, racc, rmom = r.render_moments(cfg, want_accum=True)
+            ralb, rnd = r.render_features(cfg)
+            _, single = r.denoise_guided(racc, ralb, rnd, rmom)
+            base = {"spp": spp, "frame": f, "psnr_raw": psnr_half(ref_half[f], raw),
+                    "psnr_guided": psnr_half(ref_half[f], single)}
+            for stride in (0, 1):
+                for n in TEMPORAL_PRECEDING:
+                    steps = frames_of(scene, cfg, sequence(f, n), stride)
+                    h = accumulate(steps, tparams)
+                    _, lib = r.denoise_guided(h[1], h[3], h[4], h[2])
+                    _, rec = r.denoise_guided(h[1], h[3], h[4], h[2], gparams)
+                    # the kernel is a fraction of a millisecond: the mean of 20 runs back to back
+                    prev = accumulate(steps[:-1], tparams)
+                    _, ms, _ = timed(lambda: [r.temporal_accumulate(*steps[-1], prev, tparams) for _ in range(20)][-1])
+                    row = dict(base, seed_stride=stride, preceding=n, psnr_temporal=psnr_half(ref_half[f], tonemapped(h[1])),
+                               psnr_temporal_guided=psnr_half(ref_half[f], rec),
+                               psnr_temporal_guided_library_sigma=psnr_half(ref_half[f], lib),
+                               found_history=float((h[2][..., 3] > steps[-1][2][..., 3]).float().mean()),
+                               temporal_ms=ms / 20)
+                    table.append(row)
+                    print(json.dumps(row), flush=True)
+        scene.close()
+    result["table"] = table
+    os.makedirs(args.out, exist_ok=True)
+    dump_rows_compact(result, os.path.join(args.out, "temporal_study.json"))
+    print("wrote", os.path.join(args.out, "temporal_study.json"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--guided", action="store_true")
+    ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_study"))
     args = ap.parse_args()
     if args.guided:
         return guided_study(args)
+    if args.temporal:
+        return temporal_study(args)
     r = P.GpuRenderer(0)
     result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP},
               "device": torch.cuda.get_device_name(0)}
