@@ -405,6 +405,59 @@ int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_
                             const ptg_float4* hist_albedo, const ptg_float4* hist_normal_depth,
                             ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra);
 
+/* ---- adaptive sampling ----------------------------------------------------
+ * A render that stops sampling a pixel once its mean is known well enough.
+ * cfg->samples_per_pixel = N is the budget (the frame is set up for it: N / m
+ * subframes, m = samples_per_motion_blur_step), spent in `passes` passes of
+ * N / passes samples.  Pass k owns the subframes k, k + passes, ...: its local
+ * sample jj is sample ((jj / m) * passes + k) * m + jj % m of the frame, so
+ * every pass covers the whole shutter.  A pixel adds the samples of the
+ * passes it takes, in pass order and in jj order inside a pass, into the
+ * running sums ptg_render_moments keeps (radiance sum; s1, s2, n over the
+ * finite samples, all from +0).  After pass k, when min_passes <= k + 1 <
+ * passes, every pixel of the rectangle is judged on its current sums:
+ *   noisy = n < 2 || !(vm <= tol * tol),  tol = threshold * (m1 + luminance_floor),
+ *   m1 = s1/n, m2 = s2/n, vm = max(m2 - m1*m1, 0) / (n - 1)
+ * and a pixel takes pass k + 1 if any pixel of its (2 dilate + 1)^2 window,
+ * clipped to the rectangle, is noisy.  The rule keeps no state: a pixel that
+ * stopped is woken again by a neighbour that turns noisy.  Before min_passes
+ * every pixel is active; when no pixel is, the render ends.  Every operation
+ * is one float32 rounding (DESIGN.md 4.14 is the definition, the package's
+ * adaptive.adaptive_reference the CPU restatement, bit for bit).
+ * With passes = 1 the three image outputs are ptg_render_moments' bits. */
+typedef struct {
+    uint32_t passes;        /* 1..16; N must be a multiple of passes * samples_per_motion_blur_step */
+    uint32_t min_passes;    /* 1..passes: passes every pixel takes before the first selection */
+    uint32_t dilate;        /* 0..2: radius of the window a noisy pixel keeps awake */
+    float threshold;        /* relative standard error of the mean luminance a pixel stops at */
+    float luminance_floor;  /* added to the mean, so a dark pixel has a tolerance too */
+} ptg_adaptive_params;
+void ptg_adaptive_params_default(ptg_adaptive_params* params);
+/* Rectangle as for ptg_render.  Outputs, DEVICE pointers, [h][w], each
+ * optional but at least one given; with ns = (passes the pixel took) * N / passes:
+ *   out_accum   = radiance sum / (float)ns per channel, w = 0 (the pixel's own
+ *                 count, not N);  out_bgra = tonemap_pixel of it;
+ *   out_moments = (m1, m2, vm, (float)n) in ptg_render_moments' layout, for
+ *                 ptg_denoise_guided and ptg_temporal_accumulate as they are;
+ *   out_samples = ns (uint32).
+ * Runs on the wavefront pipeline at every ptg_set_concurrency level with the
+ * same bits; under ptg_set_pipeline(ctx, 1), or with a parameter outside the
+ * ranges above, a threshold or floor that is not positive and finite, or an
+ * N that passes * samples_per_motion_blur_step does not divide, it is
+ * PTG_E_INVALID and launches nothing.  The call WAITS on the context's
+ * stream once per selection: the host reads the 4-byte length of the next
+ * pass's pixel list (nothing else is read back); the last pass and the
+ * outputs are queued asynchronously as ptg_render's are. */
+int ptg_render_adaptive(ptg_context* ctx, const ptg_render_config* cfg,
+                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                        const ptg_adaptive_params* params,
+                        ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments,
+                        uint32_t* out_samples);
+/* The last ptg_render_adaptive call of the context: the passes it ran and the
+ * active pixel count of each (active[k] = 0 from passes_run on).  The samples
+ * it took are the sum of active[k] * N / passes. */
+int ptg_last_adaptive_stats(ptg_context* ctx, uint32_t* passes_run, uint64_t active[16]);
+
 /* Work counters of the last ptg_render* call (filled only while counting is
  * on, ptg_counters_enable; counting uses a separate, slower build of the
  * kernels):

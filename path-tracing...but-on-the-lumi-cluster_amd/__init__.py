@@ -13,6 +13,8 @@ Python identifier).  Layout:
   denoise.py       the parameter structures and the CPU restatements of
                    ptg_denoise, ptg_denoise_guided and ptg_temporal_accumulate
                    (NumPy float32 + the C library's exp)
+  adaptive.py      AdaptiveParams and the CPU restatement of ptg_render_adaptive
+                   (adaptive sampling over per-sample radiance)
   distributed.py   one process per GPU: tile / frame sharding, RCCL gather
   validator.py     validator.py-equivalent PSNR check (numpy)
   assets.py        scene asset preparation (reference OBJs + substitutes)

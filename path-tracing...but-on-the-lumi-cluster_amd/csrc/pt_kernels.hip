@@ -17,6 +17,10 @@
 //                   or DenoiseGuidedStep (variance-guided)
 //   k_temporal_accumulate  last frame's radiance and moments, reprojected
 //                   and blended with this frame's by sample count
+//   k_ad_select<ALL>, k_ad_camera, k_ad_fold, k_ad_resolve
+//                   adaptive sampling (ptg_render_adaptive): the stopping rule
+//                   compacted into a pixel list, the camera kernel and the
+//                   fold over that list, the final division
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
@@ -1247,6 +1251,201 @@ __global__ __launch_bounds__(kBlock) void k_temporal_accumulate(TemporalArgs a, 
     if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
 }
 
+// ---- adaptive sampling ----
+
+// A pass of ptg_render_adaptive: the rectangle its pixel ids index, the pass's
+// share of the frame's subframes, and the ids of the pixels it samples.
+struct AdaptivePass {
+    uint32_t x0, y0, w, h;          // rectangle: pixel id = row * w + column
+    uint32_t passes, pass, m;       // the pass owns subframes pass, pass + passes, ...; m samples each
+    const uint32_t* list;           // the active pixels' ids
+    uint32_t len;
+
+    // local sample index of the pass -> sample index of the frame
+    __device__ __forceinline__ uint32_t sample(uint32_t jl) const { return ((jl / m) * passes + pass) * m + jl % m; }
+};
+
+// The stopping rule on a pixel's running sums (s1, s2, n as bits, -): fewer
+// than 2 finite samples, or the variance of the mean above (threshold * (mean
+// + floor))^2; a NaN on either side of the comparison is noisy.
+__device__ __forceinline__ bool ad_noisy(float4 mom, float threshold, float luminance_floor)
+{
+    const uint32_t n = __float_as_uint(mom.z);
+    if(n < 2u) return true;
+    const float nf = (float)n;
+    const float m1 = mom.x / nf, m2 = mom.y / nf;
+    const float d = m2 - m1 * m1;
+    const float var = d > 0.0f ? d : 0.0f;
+    const float vm = var / (nf - 1.0f);
+    const float tol = threshold * (m1 + luminance_floor);
+    return !(vm <= tol * tol);
+}
+
+// Select and compact, one work-item per rectangle pixel: the pixel is active
+// if any pixel of its (2 dilate + 1)^2 window, clipped to the rectangle, is
+// noisy.  Active ids are appended per block - a ballot per wave, one atomic
+// per block - in pixel order inside the block, so a row's neighbours stay
+// neighbours in the list (the walks' coherence rests on 8-pixel groups); the
+// order of the blocks is whatever the atomics give, and no result depends on
+// it.  ALL: every pixel is active and the list is the identity (no atomics;
+// *count is not touched).
+template<bool ALL>
+__global__ __launch_bounds__(kBlock) void k_ad_select(uint32_t w, uint32_t h, uint32_t dilate, float threshold,
+                                                      float luminance_floor, const float4* __restrict__ mom,
+                                                      uint32_t* __restrict__ list, uint32_t* __restrict__ count)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t npix = w * h;
+    if constexpr(ALL)
+    {
+        if(p < npix) list[p] = p;
+        return;
+    }
+    bool active = false;
+    if(p < npix)
+    {
+        const int32_t x = (int32_t)(p % w), y = (int32_t)(p / w), r = (int32_t)dilate;
+        for(int32_t dy = -r; dy <= r; ++dy)
+        {
+            const int32_t qy = y + dy;
+            if(qy < 0 || qy >= (int32_t)h) continue;
+            for(int32_t dx = -r; dx <= r; ++dx)
+            {
+                const int32_t qx = x + dx;
+                if(qx < 0 || qx >= (int32_t)w) continue;
+                active = active || ad_noisy(mom[size_t(qy) * w + size_t(qx)], threshold, luminance_floor);
+            }
+        }
+    }
+    __shared__ uint32_t wave_count[kBlock / 64], block_base;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(active);
+    if(lane == 0) wave_count[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if(threadIdx.x == 0)
+    {
+        uint32_t total = 0;
+        for(uint32_t k = 0; k < kBlock / 64; ++k) total += wave_count[k];
+        block_base = total ? atomicAdd(count, total) : 0u;
+    }
+    __syncthreads();
+    if(!active) return;
+    uint32_t pos = block_base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    for(uint32_t k = 0; k < wave; ++k) pos += wave_count[k];
+    list[pos] = p;   // pos < the number of active pixels <= npix
+}
+
+// k_wf_camera over a pixel list with the pass's strided sample map: queue
+// position, PathSoA records, dead lanes and out[slot] exactly as k_wf_camera
+// writes them for a map of ad.len pixels (chunk_coords: 8 list entries x 8
+// local samples per wave), so the walk, classify, shade and sky kernels run
+// on its queue unchanged.
+template<bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_ad_camera(DevScene sc, AdaptivePass ad, uint32_t j0, uint32_t nj, uint32_t M,
+                                                      PathSoA S, uint32_t* __restrict__ counts, float4* __restrict__ out,
+                                                      unsigned long long* __restrict__ counters)
+{
+    if(blockIdx.x == 0 && threadIdx.x == 0) counts[0] = M;
+    uint32_t lives = 0;
+    for(uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x)
+    {
+        uint32_t p, jj;
+        chunk_coords(i, nj, p, jj);
+        const bool in_chunk = p < ad.len && jj < nj;
+        const uint32_t pix = in_chunk ? ad.list[p] : 0xFFFFFFFFu;
+        const uint32_t slot = in_chunk ? jj * ad.len + p : 0xFFFFFFFFu;
+        if(!in_chunk || pix >= ad.w * ad.h)
+        {
+            if(in_chunk) st_out(out + slot, make_float4(0.f, 0.f, 0.f, 0.f));
+            st_state(S.meta + i, make_uint4(slot, META_DEAD, kBePop, 0u));   // no TLAS: the walk ends at once
+            st_state(S.ray_o + i, make_float4(0.f, 0.f, 0.f, 0.f));
+            st_state(S.ray_d + i, make_float4(0.f, 0.f, 1.f, 0.f));
+            continue;
+        }
+        const uint32_t x = ad.x0 + pix % ad.w, y = ad.y0 + pix / ad.w;
+        const int32_t j = (int32_t)ad.sample(j0 + jj);
+        const uint8_t* sf = subframe_of(sc, j);
+        u4 seed;
+        f3 o, d;
+        camera_ray(sc, sf, x, y, j, seed, o, d);
+        const uint32_t sub = (uint32_t)(sf - sc.subframes) / SF_STRIDE;
+        st_state(S.meta + i, make_uint4(slot, meta_pack(0, false, sub), sc.tlas_root[sub], 0u));
+        st_state(S.seed + i, to_uint4(seed));
+        st_state(S.ray_o + i, make_float4(o.x, o.y, o.z, 0.f));
+        st_state(S.ray_d + i, make_float4(d.x, d.y, d.z, 0.f));
+        ++lives;
+    }
+    if(COUNT) flush_counters(Counters{}, counters, lives);
+}
+
+// The fold over the list: position q adds its chunk samples, in local sample
+// order, into the running sums of the pixel it names - k_accumulate<true>'s
+// operations on acc[pixel] = (sum.xyz, samples taken as bits) and mom[pixel] =
+// (s1, s2, n as bits, -), both zeroed before the first pass.  A pixel that is
+// not on the list keeps its sums.
+__global__ __launch_bounds__(kBlock) void k_ad_fold(AdaptivePass ad, uint32_t nj, const float4* __restrict__ samples,
+                                                    float4* __restrict__ acc, float4* __restrict__ mom)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if(q >= ad.len) return;
+    const uint32_t pix = ad.list[q];
+    if(pix >= ad.w * ad.h) return;
+    const float4 a = acc[pix], mo = mom[pix];
+    float ax = a.x, ay = a.y, az = a.z;
+    float s1 = mo.x, s2 = mo.y;
+    uint32_t n = __float_as_uint(mo.z);
+    for(uint32_t j = 0; j < nj; ++j)
+    {
+        const float4 s = ld_out(samples + size_t(j) * ad.len + q);
+        ax = ax + s.x;
+        ay = ay + s.y;
+        az = az + s.z;
+        if(finite3(V3(s.x, s.y, s.z)))
+        {
+            const float L = lum709(s.x, s.y, s.z);
+            s1 = s1 + L;
+            s2 = s2 + L * L;
+            ++n;
+        }
+    }
+    acc[pix] = make_float4(ax, ay, az, __uint_as_float(__float_as_uint(a.w) + nj));
+    mom[pix] = make_float4(s1, s2, __uint_as_float(n), 0.f);
+}
+
+// Resolve, one work-item per rectangle pixel: the radiance sum over the
+// pixel's own sample count, its tonemap, the moments as k_accumulate<true>
+// ends, and the count.  Each output may be null.
+__global__ __launch_bounds__(kBlock) void k_ad_resolve(uint32_t npix, const float4* __restrict__ acc,
+                                                       const float4* __restrict__ mom, float4* __restrict__ out_accum,
+                                                       uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments,
+                                                       uint32_t* __restrict__ out_samples)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= npix) return;
+    const float4 a = acc[p];
+    const uint32_t ns = __float_as_uint(a.w);
+    const float nsf = (float)ns;
+    const float ax = a.x / nsf, ay = a.y / nsf, az = a.z / nsf;
+    if(out_accum) out_accum[p] = make_float4(ax, ay, az, 0.f);
+    if(out_bgra) out_bgra[p] = tonemap(V3(ax, ay, az));
+    if(out_moments)
+    {
+        const float4 mo = mom[p];
+        const uint32_t n = __float_as_uint(mo.z);
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if(n > 0)
+        {
+            const float nf = (float)n;
+            const float m1 = mo.x / nf, m2 = mo.y / nf;
+            const float d = m2 - m1 * m1;
+            const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
+            r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
+        }
+        out_moments[p] = r;
+    }
+    if(out_samples) out_samples[p] = ns;
+}
+
 // ---------------------------------------------------------------- runtime --
 
 struct DevBuf {
@@ -1341,6 +1540,9 @@ struct ptg_context {
     DevBuf mom;                            // ptg_render_moments: the running (s1, s2, n) per pixel, beside acc
     DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
     DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
+    DevBuf ad_list, ad_count;              // ptg_render_adaptive: the active pixels' ids and their number
+    uint32_t ad_passes_run = 0;            // ptg_last_adaptive_stats
+    uint64_t ad_active[16] = {};
     DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
     uint64_t last_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // k_trace launch timing (HIP events on the launch stream)
@@ -1636,8 +1838,10 @@ int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
 
 // One chunk of the wavefront pipeline on its slot's streams: the camera
 // kernel, then per bounce round the closest-hit walk, the shadow walk of the
-// previous round's NEE rays, classify, shade and sky.
-int trace_chunk_wavefront(RenderJob& job, const Piece& pc)
+// previous round's NEE rays, classify, shade and sky.  With `ad` (a pass of
+// render_adaptive) the camera kernel is k_ad_camera over the pass's pixel
+// list, pc.j counting the pass's local samples; everything after it is the same.
+int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const AdaptivePass* ad = nullptr)
 {
     ptg_context* ctx = job.ctx;
     ptg_context::Slot& sl = ctx->slot[pc.slot];
@@ -1666,8 +1870,10 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc)
     float4* out = sl.samples.as<float4>();
     PTG_HIP(hipMemsetAsync(counts, 0, kCountWords(rounds) * sizeof(uint32_t), ms));
     const dim3 grid(std::max<uint32_t>(1, std::min<uint32_t>(ctx->persistent_blocks, grid_for(lanes))));
-    if(int e = launch(ctx, K_CAMERA, ms, grid, 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, pc.j, pc.n,
-                      uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA)))
+    if(int e = ad ? launch(ctx, K_CAMERA, ms, grid, 0, k_ad_camera<true>, k_ad_camera<false>, sc, *ad, pc.j, pc.n,
+                           uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA))
+                  : launch(ctx, K_CAMERA, ms, grid, 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, pc.j, pc.n,
+                           uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA)))
         return e;
     for(uint32_t r = 0; r < rounds; ++r)
     {
@@ -1835,6 +2041,117 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
     }
     if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
         PTG_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[job.prev_slot].ev_acc, 0));   // the caller's stream sees the whole render
+#if PTG_DEBUG
+    if(int r = check_debug_tallies(ctx)) return r;
+#endif
+    return ctx->counting ? read_counters(ctx) : PTG_OK;
+}
+
+// fold_chunk for a pass of render_adaptive: k_ad_fold over the pass's list on
+// the chunk's slot stream, after the fold before it (job.prev_slot runs
+// through the whole render: a pass's first fold follows the last fold of the
+// pass before it).
+int fold_chunk_adaptive(RenderJob& job, const Piece& pc, const AdaptivePass& ad)
+{
+    ptg_context* ctx = job.ctx;
+    ptg_context::Slot& sl = ctx->slot[pc.slot];
+    const hipStream_t as = ctx->main_of(pc.slot);
+    if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
+        PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
+    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(ad.len)), 0, k_ad_fold, k_ad_fold, ad, pc.n, sl.samples.as<float4>(),
+                      ctx->acc.as<float4>(), ctx->mom.as<float4>()))
+        return r;
+    if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
+    job.prev_slot = pc.slot;
+    return PTG_OK;
+}
+
+// ptg_render_adaptive once its arguments are checked (wavefront pipeline):
+// render_map's chunk pipelines, slots and event scheme over `passes` passes of
+// N / passes samples each.  A pass traces and folds the pixels of the list in
+// ctx->ad_list (size_chunks / plan_chunks with npix = the list's length); after
+// a pass from min_passes on, k_ad_select rebuilds the list from the running
+// sums and the host reads its length - the render's only wait.  The running
+// sums are ctx->acc and ctx->mom, indexed by rectangle pixel.
+int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelMap& rect, const ptg_adaptive_params& P,
+                    float4* out_accum, uchar4* out_bgra, float4* out_moments, uint32_t* out_samples)
+{
+    ctx->ad_passes_run = 0;
+    for(uint64_t& a: ctx->ad_active) a = 0;
+    const uint32_t npix = rect.npix;
+    if(npix == 0) return PTG_OK;
+    const uint32_t span = cfg->samples_per_pixel / P.passes;
+    RenderJob job{ctx, cfg, rect, 0, span, nullptr, nullptr};
+    const uint32_t pipelines = job.pipelines = ctx->concurrency >= 2 ? kWfSlots : 1u;
+    job.rounds = cfg->max_bounces + 1;
+    job.overlap = ctx->concurrency >= 1;
+    PTG_HIP(ctx->grow(ctx->acc, size_t(npix) * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->mom, size_t(npix) * sizeof(float4)));
+    PTG_HIP(ctx->grow(ctx->ad_list, size_t(npix) * sizeof(uint32_t)));
+    PTG_HIP(ctx->grow(ctx->ad_count, 256));
+    uint32_t* list = ctx->ad_list.as<uint32_t>();
+    uint32_t* count = ctx->ad_count.as<uint32_t>();
+    float4* acc = ctx->acc.as<float4>();
+    float4* mom = ctx->mom.as<float4>();
+    if(ctx->counting)
+    {
+        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
+        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
+        job.cnt = ctx->counters.as<unsigned long long>();
+    }
+    // the sums start from +0; before min_passes every pixel is active
+    PTG_HIP(hipMemsetAsync(acc, 0, size_t(npix) * sizeof(float4), ctx->stream));
+    PTG_HIP(hipMemsetAsync(mom, 0, size_t(npix) * sizeof(float4), ctx->stream));
+    if(int r = launch_plain(ctx, grid_for(npix), k_ad_select<true>, rect.w, rect.h, 0u, 0.0f, 0.0f, mom, list, count)) return r;
+    if(pipelines > 1)
+    {   // the other slots start after what the caller queued, the zeroed sums and the first list
+        PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
+        for(uint32_t k = 1; k < pipelines; ++k)
+            PTG_HIP(hipStreamWaitEvent(ctx->slot[k].main, ctx->ev_render_start, 0));
+    }
+    job.sc = ctx->scene_args(cfg);
+    job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
+    PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * pipelines * job.spill_region) * sizeof(uint2)));
+    // the caller's stream after the render's last fold so far
+    auto join_folds = [&]() -> int {
+        if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
+            PTG_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[job.prev_slot].ev_acc, 0));
+        return PTG_OK;
+    };
+    uint32_t len = npix;
+    for(uint32_t k = 0; k < P.passes && len > 0; ++k)
+    {
+        ctx->ad_active[k] = len;
+        ctx->ad_passes_run = k + 1;
+        job.pm.npix = len;
+        if(int r = size_chunks(job, true)) return r;
+        for(uint32_t s = 0; s < pipelines; ++s)
+        {
+            PTG_HIP(ctx->grow(ctx->slot[s].samples, size_t(len) * job.chunk * sizeof(float4)));
+            PTG_HIP(ctx->grow(ctx->slot[s].state, slot_state_bytes(job.M, job.rounds)));
+            if(!carve_slot_state(ctx->slot[s].state.as<char>(), job.M, job.st[s]))
+                return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
+        }
+        const AdaptivePass ad{rect.x0, rect.y0, rect.w, rect.h, P.passes, k, cfg->samples_per_motion_blur_step, list, len};
+        for(const Piece& pc: plan_chunks(job))
+        {
+            if(int r = trace_chunk_wavefront(job, pc, &ad)) return r;
+            if(int r = fold_chunk_adaptive(job, pc, ad)) return r;
+        }
+        if(k + 1 < P.min_passes || k + 1 >= P.passes) continue;
+        // selection: every pixel of the rectangle on its current sums
+        if(int r = join_folds()) return r;
+        PTG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+        if(int r = launch_plain(ctx, grid_for(npix), k_ad_select<false>, rect.w, rect.h, P.dilate, P.threshold,
+                                P.luminance_floor, mom, list, count))
+            return r;
+        PTG_HIP(hipMemcpyAsync(&len, count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        PTG_HIP(hipStreamSynchronize(ctx->stream));
+        if(len > npix) return fail(PTG_E_RANGE, "ptg_render_adaptive: the active list is longer than the rectangle");
+    }
+    if(int r = join_folds()) return r;
+    if(int r = launch_plain(ctx, grid_for(npix), k_ad_resolve, npix, acc, mom, out_accum, out_bgra, out_moments, out_samples))
+        return r;
 #if PTG_DEBUG
     if(int r = check_debug_tallies(ctx)) return r;
 #endif
@@ -2220,6 +2537,50 @@ int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg, uint32_t 
     PixelMap pm;
     if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments);
+}
+
+void ptg_adaptive_params_default(ptg_adaptive_params* p)
+{
+    if(!p) return;
+    // the best row of tools/denoise_study.py --adaptive --sweep (profiles/denoise_study/adaptive_study.json)
+    p->passes = 8;
+    p->min_passes = 1;
+    p->dilate = 2;
+    p->threshold = 0.025f;
+    p->luminance_floor = 0.01f;
+}
+
+int ptg_render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                        const ptg_adaptive_params* params, ptg_float4* out_accum, ptg_uchar4* out_bgra,
+                        ptg_float4* out_moments, uint32_t* out_samples)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, cfg ? cfg->samples_per_pixel : 0)) return r;
+    if(!params) return fail(PTG_E_INVALID, "ptg_render_adaptive: null params");
+    const ptg_adaptive_params P = *params;
+    if(P.min_passes < 1 || P.min_passes > P.passes || P.passes > 16)
+        return fail(PTG_E_INVALID, "ptg_render_adaptive: 1 <= min_passes <= passes <= 16");
+    if(P.dilate > 2) return fail(PTG_E_INVALID, "ptg_render_adaptive: dilate is 0, 1 or 2");
+    for(float s: {P.threshold, P.luminance_floor})
+        if(!(s > 0.0f) || !std::isfinite(s))
+            return fail(PTG_E_INVALID, "ptg_render_adaptive: threshold and luminance_floor must be positive and finite");
+    if(uint64_t(cfg->samples_per_pixel) % (uint64_t(P.passes) * cfg->samples_per_motion_blur_step))
+        return fail(PTG_E_INVALID, "ptg_render_adaptive: samples_per_pixel must be a multiple of passes * samples_per_motion_blur_step");
+    if(!out_accum && !out_bgra && !out_moments && !out_samples) return fail(PTG_E_INVALID, "ptg_render_adaptive: no output given");
+    if(ctx->pipeline != 0)
+        return fail(PTG_E_INVALID, "ptg_render_adaptive: runs on the wavefront pipeline only (ptg_set_pipeline(ctx, 0))");
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
+    return render_adaptive(ctx, cfg, pm, P, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra),
+                           reinterpret_cast<float4*>(out_moments), out_samples);
+}
+
+int ptg_last_adaptive_stats(ptg_context* ctx, uint32_t* passes_run, uint64_t active[16])
+{
+    if(!ctx || !passes_run || !active) return fail(PTG_E_INVALID, "ptg_last_adaptive_stats: bad arguments");
+    *passes_run = ctx->ad_passes_run;
+    memcpy(active, ctx->ad_active, sizeof(ctx->ad_active));
+    return PTG_OK;
 }
 
 static int tile_map(const ptg_render_config* cfg, uint32_t tw, uint32_t th, uint32_t first, uint32_t stride,

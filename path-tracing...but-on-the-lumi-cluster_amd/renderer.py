@@ -220,6 +220,43 @@ class GpuRenderer:
         out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
+    # -- adaptive sampling ---------------------------------------------------
+    def render_adaptive(self, cfg: N.RenderConfig, params=None, rect=None):
+        """ptg_render_adaptive over `rect` (default: the whole image) with
+        cfg.samples_per_pixel as the budget: (bgra, accum, moments float32
+        [h, w, 4] in render_moments' layout, samples [h, w]: the samples each
+        pixel took, the library's uint32 in an int32 tensor).  The call waits for the GPU once per selection pass;
+        the outputs are queued asynchronously."""
+        import torch
+        from .adaptive import AdaptiveParams
+        p = params if params is not None else AdaptiveParams.default()
+        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+        dev = torch.device("cuda", self.device)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        accum = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        samples = torch.empty((h, w), dtype=torch.int32, device=dev)
+        N.check(N.lib().ptg_render_adaptive(self._ctx, C.byref(cfg), x0, y0, w, h, C.byref(p), _ptr(accum), _ptr(bgra),
+                                            _ptr(moments), _ptr(samples)), "ptg_render_adaptive")
+        return bgra, accum, moments, samples
+
+    def adaptive_stats(self):
+        """The last render_adaptive: the active pixel count of every pass it
+        ran (ptg_last_adaptive_stats); a pass is budget / passes samples."""
+        n = C.c_uint32()
+        active = np.zeros(16, np.uint64)
+        N.check(N.lib().ptg_last_adaptive_stats(self._ctx, C.byref(n), active.ctypes.data), "ptg_last_adaptive_stats")
+        return [int(a) for a in active[:n.value]]
+
+    def render_adaptive_denoised(self, cfg: N.RenderConfig, params=None, guided_params=None):
+        """render_adaptive + render_features + denoise_guided of the whole
+        image: (bgra, denoised radiance).  The filter reads the moments of the
+        samples each pixel took."""
+        _, acc, moments, _ = self.render_adaptive(cfg, params)
+        albedo, normal_depth = self.render_features(cfg)
+        out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, guided_params, want_bgra=True, out_radiance=acc)
+        return bgra, out
+
     # -- temporal accumulation -------------------------------------------------
     def temporal_accumulate(self, cam, radiance, moments, albedo, normal_depth, history=None, params=None,
                             want_bgra=False, out_radiance=None, out_moments=None):
@@ -393,14 +430,21 @@ class TemporalDenoiser:
     (counted from the construction or the last reset) therefore renders with
     ``student_id + k * seed_stride`` in uint32 arithmetic; frame 0 of a
     sequence has the reference's bits either way, and ``seed_stride=0`` keeps
-    the reference's seeds on every frame."""
+    the reference's seeds on every frame.
+
+    ``adaptive_params``: an ``adaptive.AdaptiveParams`` makes the step render
+    with render_adaptive (cfg.samples_per_pixel is then the budget) instead
+    of render_moments; the accumulation and the filter take its moments,
+    whose sample count varies per pixel, as they are.  None (the default)
+    renders with render_moments."""
 
     def __init__(self, renderer: GpuRenderer, cfg: N.RenderConfig, temporal_params=None, guided_params=None,
-                 seed_stride=1):
+                 seed_stride=1, adaptive_params=None):
         self.renderer = renderer
         self.cfg = cfg
         self.temporal_params = temporal_params
         self.guided_params = guided_params
+        self.adaptive_params = adaptive_params
         self.seed_stride = int(seed_stride)
         self.reset()
 
@@ -421,7 +465,10 @@ class TemporalDenoiser:
         r.upload(scene)
         subframes = scene.view()["subframes"]
         cam = N.Camera.of(subframes[len(subframes) // 2]["cam"])
-        _, acc, moments = r.render_moments(cfg, want_accum=True)
+        if self.adaptive_params is not None:
+            _, acc, moments, _ = r.render_adaptive(cfg, self.adaptive_params)
+        else:
+            _, acc, moments = r.render_moments(cfg, want_accum=True)
         albedo, normal_depth = r.render_features(cfg)
         # in place: this frame's radiance and moments become the accumulated ones
         acc, moments, _ = r.temporal_accumulate(cam, acc, moments, albedo, normal_depth, self.history, self.temporal_params,

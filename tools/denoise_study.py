@@ -34,7 +34,18 @@ guided PSNR over both frames at 16 and 64 spp after 4 preceding frames
 (ptg_temporal_params_default) are the best row of the recorded sweep.  Writes
 <out>/temporal_study.json.
 
-Usage: python tools/denoise_study.py [--guided | --temporal] [--sweep] [--out profiles/<name>]
+--adaptive studies adaptive sampling (ptg_render_adaptive) against uniform
+sampling of the same cost: budgets of 64, 256 and 1024 samples in 8 passes,
+per row the samples taken, the active pixels per pass, time and PSNR of the
+adaptive render and of ptg_render at the smallest multiple of 8 spp that takes
+at least as many samples, and the cost of the machinery alone (every pixel in
+every pass) against ptg_render_moments.  With --sweep it runs a grid of
+threshold x dilate at budgets 64 and 256 and ranks the rows by their smallest
+gain over uniform sampling of the four (frame, budget) cells; the library's
+defaults (ptg_adaptive_params_default) are the best row of the recorded sweep.
+Writes <out>/adaptive_study.json.
+
+Usage: python tools/denoise_study.py [--guided | --temporal | --adaptive] [--sweep] [--out profiles/<name>]
 Writes <out>/denoise_study.json.
 """
 import argparse
@@ -361,13 +372,176 @@ def temporal_study(args):
     print("wrote", os.path.join(args.out, "temporal_study.json"))
 
 
+ADAPTIVE_BUDGETS = (64, 256, 1024)
+ADAPTIVE_PASSES = 8
+ADAPTIVE_SWEEP_BUDGETS = (64, 256)
+ADAPTIVE_GRID = {"threshold": (0.025, 0.05, 0.1, 0.2), "dilate": (0, 1, 2)}
+ADAPTIVE_REF_SPP_1024 = 4096                     # the 1024-spp budget is judged against a 4096-spp frame
+ADAPTIVE_CHECK = {"width": 160, "height": 90, "budget": 64, "frame": 0, "reference_spp": 256}
+
+
+def adaptive_study(args):
+    """Adaptive sampling against uniform sampling of the same cost.  Per row
+    (budget N, frame, threshold, dilate; passes 8, min_passes 1, the library's
+    luminance_floor): the samples the adaptive render took, its active pixels
+    per pass, time and PSNR, beside ptg_render at the smallest multiple of 8
+    spp whose samples are at least as many (on a scene set up for that spp:
+    its subframes cover the shutter).  The 1024-spp budget is judged against
+    a 4096-spp frame, the others against the 1024-spp frame.  --sweep runs the
+    grid over budgets 64 and 256 and ranks the rows by the smallest gain over
+    uniform sampling of the four (frame, budget) cells; without it the
+    library's defaults are the only row."""
+    from ptlumi.adaptive import AdaptiveParams
+    r = P.GpuRenderer(0)
+    lib_params = AdaptiveParams.default()
+    result = {"config": {"width": W, "height": H, "frames": FRAMES, "budgets": ADAPTIVE_BUDGETS, "passes": ADAPTIVE_PASSES,
+                         "reference_spp": {str(n): ADAPTIVE_REF_SPP_1024 if n >= REF_SPP else REF_SPP
+                                           for n in ADAPTIVE_BUDGETS}},
+              "device": torch.cuda.get_device_name(0), "library_params": lib_params.as_dict()}
+    npix = W * H
+
+    def half(bgra):
+        return V.downscale_half(V.bgra_to_rgb(bgra.cpu().numpy()))
+
+    def params(threshold, dilate):
+        return AdaptiveParams.default(passes=ADAPTIVE_PASSES, min_passes=1, threshold=threshold, dilate=dilate)
+
+    # the references, and the uniform renders by (spp, frame), each on a scene set up for its spp
+    ref_half = {}
+    uniform = {}
+
+    def uniform_at(spp):
+        if (spp, FRAMES[0]) in uniform:
+            return
+        cfg = N.RenderConfig.make(W, H, spp)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene)
+            (bgra, _), ms, wall = timed(lambda: r.render(cfg))
+            uniform[spp, f] = (half(bgra), ms, wall)
+        scene.close()
+
+    for spp in sorted(set(result["config"]["reference_spp"].values())):
+        uniform_at(spp)
+        for f in FRAMES:
+            ref_half[spp, f] = uniform[spp, f][0]
+
+    def psnr(n, f, image_half):
+        """validate_frame's PSNR of a downscaled image against the budget's reference."""
+        return float(V.psnr(ref_half[ADAPTIVE_REF_SPP_1024 if n >= REF_SPP else REF_SPP, f], image_half))
+
+    grid = [dict(zip(ADAPTIVE_GRID, c)) for c in itertools.product(*ADAPTIVE_GRID.values())] if args.sweep else \
+        [{"threshold": lib_params.threshold, "dilate": lib_params.dilate}]
+    rows, machinery = [], []
+    for n in ADAPTIVE_BUDGETS:
+        cfg = N.RenderConfig.make(W, H, n)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene)
+            # the machinery's cost: every pixel takes every pass, against ptg_render_moments at N
+            every = params(1e-30, 0)
+            _, m_ms, m_wall = timed(lambda: r.render_moments(cfg, want_accum=True))
+            _, a_ms, a_wall = timed(lambda: r.render_adaptive(cfg, every))
+            taken = sum(r.adaptive_stats()) * (n // ADAPTIVE_PASSES)
+            _, d_ms, d_wall = timed(lambda: r.render_adaptive_denoised(cfg, every))
+            row = {"budget": n, "frame": f, "render_moments_ms": m_ms, "render_moments_wall_ms": m_wall,
+                   "adaptive_all_passes_ms": a_ms, "adaptive_all_passes_wall_ms": a_wall,
+                   "adaptive_all_passes_share_of_budget": taken / (npix * n),
+                   "adaptive_all_passes_filtered_ms": d_ms, "adaptive_all_passes_filtered_wall_ms": d_wall}
+            machinery.append(row)
+            print(json.dumps(row), flush=True)
+            for g in grid if n in ADAPTIVE_SWEEP_BUDGETS or not args.sweep else []:
+                p = params(**g)
+                (bgra, _, _, _), ms, wall = timed(lambda: r.render_adaptive(cfg, p))
+                active = r.adaptive_stats()
+                rows.append(dict(g, budget=n, frame=f, active=active, samples=sum(active) * (n // ADAPTIVE_PASSES),
+                                 ms=ms, wall_ms=wall, image=half(bgra)))
+        scene.close()
+
+    def finish(row):
+        """The row's PSNR and its uniform comparison."""
+        n, f = row["budget"], row["frame"]
+        spp = max(8, -(-row["samples"] // (8 * npix)) * 8)
+        uniform_at(spp)
+        u_half, u_ms, u_wall = uniform[spp, f]
+        row.update(share_of_budget=row["samples"] / (npix * n), psnr=psnr(n, f, row.pop("image")), uniform_spp=spp,
+                   uniform_psnr=psnr(n, f, u_half), uniform_ms=u_ms, uniform_wall_ms=u_wall)
+        row["gain_db"] = row["psnr"] - row["uniform_psnr"]
+        print(json.dumps(row), flush=True)
+
+    for row in rows:
+        finish(row)
+    best = {"threshold": lib_params.threshold, "dilate": lib_params.dilate}
+    if args.sweep:
+        ranked = []
+        for g in grid:
+            cells = {"%d@%d" % (x["frame"], x["budget"]): x["gain_db"] for x in rows
+                     if all(x[k] == v for k, v in g.items()) and x["budget"] in ADAPTIVE_SWEEP_BUDGETS}
+            ranked.append(dict(g, gain_db=cells, min_gain_db=min(cells.values())))
+        ranked.sort(key=lambda x: -x["min_gain_db"])
+        best = {k: ranked[0][k] for k in ADAPTIVE_GRID}
+        result["sweep"] = {"budgets": ADAPTIVE_SWEEP_BUDGETS, "grid": ADAPTIVE_GRID, "best": ranked[0], "rows": ranked}
+        print("sweep: best", ranked[0], flush=True)
+        # the best row at the budgets the sweep left out
+        for n in ADAPTIVE_BUDGETS:
+            if n in ADAPTIVE_SWEEP_BUDGETS:
+                continue
+            cfg = N.RenderConfig.make(W, H, n)
+            scene = N.Scene(ASSETS, cfg)
+            for f in FRAMES:
+                scene.setup_frame(f)
+                r.upload(scene)
+                p = params(**best)
+                (bgra, _, _, _), ms, wall = timed(lambda: r.render_adaptive(cfg, p))
+                active = r.adaptive_stats()
+                rows.append(dict(best, budget=n, frame=f, active=active, samples=sum(active) * (n // ADAPTIVE_PASSES),
+                                 ms=ms, wall_ms=wall, image=half(bgra)))
+                finish(rows[-1])
+            scene.close()
+    result["params"] = dict(lib_params.as_dict(), passes=ADAPTIVE_PASSES, min_passes=1, **best)
+
+    # the small end-to-end check of the suite, with the best row: no downscale
+    c = ADAPTIVE_CHECK
+    cnp = c["width"] * c["height"]
+
+    def check_render(spp, adaptive):
+        cfg = N.RenderConfig.make(c["width"], c["height"], spp)
+        scene = N.Scene(ASSETS, cfg)
+        scene.setup_frame(c["frame"])
+        r.upload(scene)
+        bgra = r.render_adaptive(cfg, params(**best))[0] if adaptive else r.render(cfg)[0]
+        r.synchronize()
+        scene.close()
+        return V.bgra_to_rgb(bgra.cpu().numpy())
+
+    check_ref = check_render(c["reference_spp"], False)
+    ad = check_render(c["budget"], True)
+    active = r.adaptive_stats()
+    spp = max(8, -(-sum(active) * (c["budget"] // ADAPTIVE_PASSES) // (8 * cnp)) * 8)
+    result["check"] = dict(c, active=active, uniform_spp=spp, psnr=float(V.psnr(check_ref, ad)),
+                           uniform_psnr=float(V.psnr(check_ref, check_render(spp, False))))
+    result["check"]["gain_db"] = result["check"]["psnr"] - result["check"]["uniform_psnr"]
+    print("check:", json.dumps(result["check"]), flush=True)
+
+    result["machinery"] = machinery
+    result["table"] = rows
+    os.makedirs(args.out, exist_ok=True)
+    dump_rows_compact(result, os.path.join(args.out, "adaptive_study.json"))
+    print("wrote", os.path.join(args.out, "adaptive_study.json"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--guided", action="store_true")
     ap.add_argument("--temporal", action="store_true")
+    ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_study"))
     args = ap.parse_args()
+    if args.adaptive:
+        return adaptive_study(args)
     if args.guided:
         return guided_study(args)
     if args.temporal:
