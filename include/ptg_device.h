@@ -151,6 +151,10 @@ __host__ __device__ inline ptg_uchar4 tonemap_pixel(ptg_float3 color)
  *   bit 5  fmin's tie rule (glibc: equal operands give the second)
  *   bit 6  float division and reciprocal, correctly rounded (the walk's
  *          reciprocals and -fhip-fp32-correctly-rounded-divide-sqrt)
+ *   bit 7  below_radius(s) against sqrtf(s) - R < 0 at pred(T), T, 0, +inf, NaN
+ *   bit 8  pow5_d / pow_quarter_d (the certified surface pass's constant-
+ *          exponent pow) against this host's pow: the same bits at 0 and 1,
+ *          the same sign or NaN, and within kMaxLibDist ulps elsewhere
  * The SLP vectoriser's divergence shows only inside a
  * whole BVH walk; tests/test_gpu_parity.py's ray records catch it. */
 namespace ptg_selftest {
@@ -163,6 +167,10 @@ struct Io {
     ptg_uchar4 tone_out[kArgs];
     float tie_out[2];
     float div_out[kArgs], rcp_out[kArgs];
+    float s[kArgs];                 /* below_radius arguments (the first 5 are used) */
+    int below_out[kArgs], below_sqrt_out[kArgs];
+    float p[kArgs];                 /* pow5_d / pow_quarter_d arguments */
+    double pow5_out[kArgs], powq_out[kArgs];
 };
 /* internal linkage: several translation units of one library may include
  * this header (tests/device_dropin builds a two-TU library to check it) */
@@ -181,6 +189,10 @@ __global__ void kernel(Io* io)
         io->tone_out[i] = tonemap_pixel(io->colors[i]);
         io->div_out[i] = io->a / io->x[i];
         io->rcp_out[i] = ptg::dm::rcp_rn(io->x[i]);
+        io->below_out[i] = ptg::dm::below_radius(io->s[i]);
+        io->below_sqrt_out[i] = ptg::dm::fsqrt(io->s[i]) - ptg::dm::kBelowEarthRadius < 0;
+        io->pow5_out[i] = ptg::dm::pow5_d((double)io->p[i]);
+        io->powq_out[i] = ptg::dm::pow_quarter_d((double)io->p[i]);
     }
     io->tie_out[0] = ptg::dm::gmin(io->c - io->c, -(io->c - io->c));   /* fmin(+0, -0): -0 */
     io->tie_out[1] = ptg::dm::gmax(-(io->c - io->c), io->c - io->c);   /* fmax(-0, +0): +0 */
@@ -188,6 +200,17 @@ __global__ void kernel(Io* io)
 } // namespace
 inline bool same(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
 inline bool samef(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
+/* a fast double against the host library's: both NaN, or the same sign and at
+ * most `ulps` adjacent doubles apart */
+inline bool near(double got, double want, long long ulps)
+{
+    if(got != got || want != want) return got != got && want != want;
+    long long a, b;
+    memcpy(&a, &got, sizeof a);
+    memcpy(&b, &want, sizeof b);
+    if((a < 0) != (b < 0)) return false;
+    return (a > b ? a - b : b - a) <= ulps;
+}
 } // namespace ptg_selftest
 
 static inline int ptg_device_selftest(hipStream_t stream = nullptr)
@@ -203,6 +226,11 @@ static inline int ptg_device_selftest(hipStream_t stream = nullptr)
         h.x[i] = xs[i];
         h.colors[i].x = xs[i] * 0.5f; h.colors[i].y = xs[i]; h.colors[i].z = xs[i] * 2.0f;
     }
+    /* pred(T), T (ref_math.h kBelowEarthBits), 0, +inf, NaN */
+    const uint32_t sbits[5] = {ptg::dm::kBelowEarthBits - 1u, ptg::dm::kBelowEarthBits, 0u, 0x7f800000u, 0x7fc00000u};
+    memcpy(h.s, sbits, sizeof sbits);
+    const float ps[kArgs] = {0.0f, 1.0f, -2.5f, 0.3f, 0.7531f, 3.0f, 1e-30f, 1e30f};
+    memcpy(h.p, ps, sizeof ps);
     Io* d = nullptr;
     hipError_t e = hipMalloc(&d, sizeof(Io));
     if(e == hipSuccess) e = hipMemcpyAsync(d, &h, sizeof(Io), hipMemcpyHostToDevice, stream);
@@ -229,6 +257,15 @@ static inline int ptg_device_selftest(hipStream_t stream = nullptr)
         if(!samef(r.div_out[i], h.a / h.x[i]) || !samef(r.rcp_out[i], 1.0f / h.x[i])) bad |= 64;
     }
     if(!samef(r.tie_out[0], -0.0f) || !samef(r.tie_out[1], 0.0f)) bad |= 32;
+    const int below_want[5] = {1, 0, 1, 0, 0};
+    for(int i = 0; i < 5; ++i)
+        if(r.below_out[i] != below_want[i] || r.below_sqrt_out[i] != below_want[i]) bad |= 128;
+    for(int i = 0; i < kArgs; ++i)
+    {
+        const double x = (double)h.p[i];
+        const long long ulps = i < 2 ? 0 : (long long)ptg::dm::kMaxLibDist;
+        if(!near(r.pow5_out[i], pow(x, 5.0), ulps) || !near(r.powq_out[i], pow(x, 0.25), ulps)) bad |= 256;
+    }
     return bad;
 }
 

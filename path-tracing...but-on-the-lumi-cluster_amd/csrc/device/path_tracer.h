@@ -20,6 +20,7 @@ namespace ptg {
 namespace dm {
 
 constexpr float EARTH_RADIUS = 6.3781e6f;
+static_assert(EARTH_RADIUS == kBelowEarthRadius, "below_radius (ref_math.h) is derived for this radius");
 constexpr float ATMOSPHERE_HEIGHT = 1.0e5f;
 constexpr float RAYLEIGH_SCALE_HEIGHT = 7994.0f;
 constexpr float MIE_SCALE_HEIGHT = 1200.0f;
@@ -1486,7 +1487,8 @@ PTG_D AttenSteps attenuation_steps(float jitter, f3 pos, f3 view, float tmax)
     for(int i = 0; i < PRIMARY_ITERATIONS; ++i)
     {
         const float t = a.segment * (jitter + (float)i);
-        if(length((pos + t * view) - earth) - EARTH_RADIUS < 0)
+        const f3 v = (pos + t * view) - earth;
+        if(below_radius(dot(v, v)))   // length(v) - EARTH_RADIUS < 0, without the sqrt
         {
             a.blocked = true;
             return a;
@@ -1549,7 +1551,8 @@ PTG_D void atmosphere_scattering(u4& seed, const Light& L, f3 pos, f3 view, floa
         for(int j = 0; j < SECONDARY_ITERATIONS; ++j)
         {
             const float tt = light_segment * (jitter.y + (float)j);
-            if(length((p + tt * L.dir) - earth) - EARTH_RADIUS < 0) shadowed = true;
+            const f3 v = (p + tt * L.dir) - earth;
+            if(below_radius(dot(v, v))) shadowed = true;   // length(v) - EARTH_RADIUS < 0
         }
         if(!shadowed)
             for(int j = 0; j < SECONDARY_ITERATIONS; ++j)

@@ -113,6 +113,19 @@ PTG_D float fsqrt(float x) { return __builtin_sqrtf(x); }
 PTG_D float length(f3 a) { return fsqrt(dot(a, a)); }
 PTG_D f3 normalize(f3 a) { return a / length(a); }
 
+// length(v) - EARTH_RADIUS < 0 from s = dot(v, v) alone, without the square
+// root.  The subtraction of two floats is negative exactly when the first is
+// the smaller (denormals kept, so a difference never rounds to zero), and a
+// correctly rounded sqrt is monotone, so there is one float T with
+// sqrtf(s) < R  <=>  s < T: for R = 6378100.0f, T has the bits below
+// (sqrtf(T) = R, sqrtf(pred(T)) = R - 0.5).  Domain: every float s >= 0, +0
+// and +inf included; NaN is false on both sides; a dot product of a vector
+// with itself is never negative.  tests/test_below_radius.py checks T on the
+// host, tools/exhaustive.hip all 2^32 patterns on the device.
+constexpr float kBelowEarthRadius = 6378100.0f;   // == path_tracer.h EARTH_RADIUS (static_assert there)
+constexpr uint32_t kBelowEarthBits = 0x5613fe5au;  // 40680160231424.0f = 0x1.27fcb4p+45f
+PTG_D bool below_radius(float s) { return s < __uint_as_float(kBelowEarthBits); }
+
 // glibc fminf/fmaxf (x86_64 minss/maxss + NaN fix-up): ties return y.
 PTG_D float gmin(float x, float y) { return (x < y || y != y) ? x : y; }
 PTG_D float gmax(float x, float y) { return (x > y || y != y) ? x : y; }
@@ -155,8 +168,10 @@ PTG_D float fexp(float x) { return (float)exp((double)x); }
 // algorithms, glibc_math.h) everywhere else, MathFast in those two kernels.
 //  * D: over every float argument, ocml's double is at most D ulps from
 //    glibc's (tools/exhaustive_f64.hip "distance" rows, profiles/r03_exhaustive/:
-//    exp, sin, cos, pow(x, 5 / 1.5 / 0.25) all 1); kMaxLibDist = 4 is the
-//    largest D the bounds below are sized for.
+//    exp, sin, cos, pow(x, 5 / 1.5 / 0.25) all 1; and MathFast's own forms
+//    of the two constant-exponent powers, pow5_d and pow_quarter_d below,
+//    1 and 1: profiles/r08_fastpaths/); kMaxLibDist = 4 is the largest D
+//    the bounds below are sized for.
 //  * each wrapper states how far its double v can then be from the double
 //    the same expression gives with glibc's value: K ulps of v, K <= 4 (D + 1)
 //    (a relative error eps is at most eps 2^53 ulps; two values on either side
@@ -229,6 +244,34 @@ struct MathFast {    // ocml's, certified; fail_mask: bit CS_x when a certificat
 // float ties, which no rounding certificate covers).
 PTG_D bool pow_exact_arg(double x, double y) { return x == 1.0 || (x == 0.0 && y > 0.0); }
 
+// MathFast's pow for the two constant exponents of the surface pass, in place
+// of ocml's generic log + exp routine.  x is a float widened to double in both.
+//  * pow5_d: x * x is exact (48 significant bits), so x^5 carries the two
+//    roundings of x2 * x2 and x4 * x; no float's fifth power leaves double's
+//    normal range; signs, zeros, inf and NaN come out as pow's.
+//  * pow_quarter_d: two correctly rounded square roots.  x + 0.0 turns -0 into
+//    +0, as pow(-0, 0.25) = +0 (sqrt(-0) is -0), and -inf takes +inf's place,
+//    as pow(-inf, 0.25) = +inf (C99 F.9.4.4); any other negative x gives NaN,
+//    +inf gives +inf, as pow's.
+// Their distance D from glibc's pow over every float argument, measured
+// (tools/exhaustive_f64.hip "distance pow5_d / pow_quarter_d" rows,
+// profiles/r08_fastpaths/): 1 ulp for each, as ocml's pow; D <= kMaxLibDist
+// is all the certificates below ask of a fast double, and at pow_exact_arg's
+// arguments both are exact.
+PTG_D double pow5_d(double x)
+{
+    const double x2 = x * x, x4 = x2 * x2;
+    return x4 * x;
+}
+PTG_D double pow_quarter_d(double x) { return sqrt(sqrt(x < -0x1.fffffffffffffp+1023 ? -x : x + 0.0)); }
+// y is a literal at every call site: the comparison folds
+PTG_D double pow_fast(double x, double y)
+{
+    if(y == 5.0) return pow5_d(x);
+    if(y == 0.25) return pow_quarter_d(x);
+    return pow(x, y);
+}
+
 // (float)((double)acc + exp(x)), acc >= 0: the sum is at least exp(x), so
 // D ulps of exp(x) plus the two roundings is <= 2 (D + 1) ulps of the sum
 // (the factor 2: the two sums may lie in adjacent binades).
@@ -250,11 +293,12 @@ template<class MP> PTG_D float exp_times(double x, float s, MP& mp)
 }
 // (float)((double)a + (double)b * pow(x, y)), a, b >= 0: the product is off by
 // <= 2 D + 1 ulps of itself, the sum (>= the product) by one rounding more:
-// <= 2 (2 D + 2) ulps of the sum.
+// <= 2 (2 D + 2) ulps of the sum.  The fast pow is pow_fast: pow5_d at the
+// path's y = 5 (D = 1, measured), ocml's otherwise.
 template<class MP> PTG_D float add_mul_pow(float a, float b, double x, double y, MP& mp)
 {
     if constexpr(!MP::kFast) return (float)((double)a + (double)b * glibc::pow(x, y));
-    const double v = (double)a + (double)b * pow(x, y);
+    const double v = (double)a + (double)b * pow_fast(x, y);
     mp.check(pow_exact_arg(x, y) || (a >= 0.0f && b >= 0.0f && float_certain(v)), v, CS_ADD_MUL_POW);
     return (float)v;
 }
@@ -282,7 +326,8 @@ template<class MP> PTG_D float times_sin(float s, double phi, MP& mp)
     mp.check(phi == 0.0 || float_certain(v), v, CS_TIMES_SIN);
     return (float)v;
 }
-// (float)((double)r * max(1 - g / pow(x, y), 0)), r >= 0.  q = g / pow is off
+// (float)((double)r * max(1 - g / pow(x, y), 0)), r >= 0, the fast pow being
+// pow_fast (pow_quarter_d at the path's y = 0.25, D = 1).  q = g / pow is off
 // by <= 2 D + 1 ulps of q.  q > 1 + 2^-48: both q exceed 1, the result is
 // r * 0.  Otherwise w = 1 - q (exact for q in [0.5, 1], Sterbenz) is off by
 // (2 D + 1) 2^s + 1 ulps of w, s = exponent of q minus exponent of w (s <= 0
@@ -291,7 +336,7 @@ template<class MP> PTG_D float times_sin(float s, double phi, MP& mp)
 template<class MP> PTG_D float times_one_minus_div_pow(float r, double g, double x, double y, MP& mp)
 {
     if constexpr(!MP::kFast) return (float)((double)r * gmax_d(1.0 - g / glibc::pow(x, y), 0.0));
-    const double q = g / pow(x, y);
+    const double q = g / pow_fast(x, y);
     const double w = gmax_d(1.0 - q, 0.0);
     const double v = (double)r * w;
     const int32_t s = int32_t((uint64_t)__double_as_longlong(q) >> 52 & 0x7ff) -

@@ -4,6 +4,9 @@
 //   rcp_rn(x)        vs 1.0f / x        (the walk's reciprocals)
 //   div_by(x, c, rc) vs x / c           (c = the Rayleigh and Mie scale heights)
 //   sqrt_rn(x)       vs sqrtf(x)        (fsqrt: lengths, sphere tests, sampling)
+//   below_radius(s)  vs sqrtf(s) - R < 0  (the atmosphere's below-ground tests; every
+//                                          pattern but the negative numbers, which a
+//                                          dot(v, v) never is: -0, inf and NaNs included)
 // Run once on the GPU box (tools/exhaustive.sh); it is what licenses these
 // functions in place of the IEEE operations in a bit-exact hot path.
 #include <hip/hip_runtime.h>
@@ -14,7 +17,7 @@
 
 using namespace ptg::dm;
 
-enum { OP_RCP, OP_DIV, OP_SQRT };
+enum { OP_RCP, OP_DIV, OP_SQRT, OP_BELOW };
 
 __global__ void k_check(int op, uint64_t begin, uint64_t count, float c, float rc, unsigned long long* mismatches, uint32_t* first)
 {
@@ -25,7 +28,13 @@ __global__ void k_check(int op, uint64_t begin, uint64_t count, float c, float r
         float want, got;
         if(op == OP_RCP) { want = 1.0f / x; got = rcp_rn(x); }
         else if(op == OP_DIV) { want = x / c; got = div_by(x, c, rc); }
-        else { want = __builtin_sqrtf(x); got = sqrt_rn(x); }
+        else if(op == OP_SQRT) { want = __builtin_sqrtf(x); got = sqrt_rn(x); }
+        else
+        {
+            if(x < 0.0f) continue;   // outside the predicate's domain
+            want = fsqrt(x) - kBelowEarthRadius < 0 ? 1.0f : 0.0f;   // length(v) - EARTH_RADIUS < 0
+            got = below_radius(x) ? 1.0f : 0.0f;
+        }
         const bool same = __float_as_uint(want) == __float_as_uint(got) || (want != want && got != got);
         if(!same)
         {
@@ -42,6 +51,7 @@ int main()
         {OP_DIV, 7994.0f, "div_by(x, 7994) vs x / 7994"},    // RAYLEIGH_SCALE_HEIGHT (path_tracer.h)
         {OP_DIV, 1200.0f, "div_by(x, 1200) vs x / 1200"},    // MIE_SCALE_HEIGHT
         {OP_SQRT, 0.0f, "sqrt_rn(x) vs sqrtf(x)"},
+        {OP_BELOW, 0.0f, "below_radius(s) vs sqrtf(s) - 6378100.0f < 0, s not negative"},
     };
     unsigned long long* d_mis;
     uint32_t* d_first;

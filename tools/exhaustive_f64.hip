@@ -39,16 +39,18 @@
 
 using namespace ptg::dm;
 
-enum Fn { F_EXP, F_LOG, F_SIN, F_COS, F_SQRT, F_POW5, F_POW025, F_POW15, F_POWSRGB, F_INVERF, F_FSIN, F_FCOS, F_FEXP, F_DEXP, F_DSIN, F_DCOS, F_DPOW5, F_DPOW15, F_DPOW025, F_COUNT };
+enum Fn { F_EXP, F_LOG, F_SIN, F_COS, F_SQRT, F_POW5, F_POW025, F_POW15, F_POWSRGB, F_INVERF, F_FSIN, F_FCOS, F_FEXP, F_DEXP, F_DSIN, F_DCOS, F_DPOW5, F_DPOW15, F_DPOW025, F_DPOW5FAST, F_DPOWQFAST, F_COUNT };
 // F_D*: "distance" rows - ocml's double (the certified shading, ref_math.h) against glibc's: the
-// largest distance in ulps over all float arguments, which must not exceed kMaxLibDist
+// largest distance in ulps over all float arguments, which must not exceed kMaxLibDist;
+// the last two are pow5_d / pow_quarter_d, MathFast's forms of pow(x, 5.0) / pow(x, 0.25)
 static bool is_distance(int fn) { return fn >= F_DEXP; }
 static const char* kNames[F_COUNT] = {"exp(x)", "log(x)", "sin(x), |x| < 105414350", "cos(x), |x| < 105414350",
                                       "sqrt(x)", "pow(x, 5.0)", "pow(x, 0.25)", "pow(x, 1.5)",
                                       "pow(x, (double)(1.0f / 2.4f))", "inv_erf(x), |x| <= 1 - 1e-6",
                                       "(float)sin(x) (fsin)", "(float)cos(x) (fcos)", "(float)exp(x) (fexp)",
                                       "distance ocml exp(x)", "distance ocml sin(x)", "distance ocml cos(x)",
-                                      "distance ocml pow(x, 5.0)", "distance ocml pow(x, 1.5)", "distance ocml pow(x, 0.25)"};
+                                      "distance ocml pow(x, 5.0)", "distance ocml pow(x, 1.5)", "distance ocml pow(x, 0.25)",
+                                      "distance pow5_d(x) from pow(x, 5.0)", "distance pow_quarter_d(x) from pow(x, 0.25)"};
 constexpr float kErfLimit = 1.0f - 1e-6f;   // sample_gaussian's clamp (path_tracer.hh:12-17)
 constexpr float kSinCosLimit = 105414350.0f;   // glibc's reduce_sincos range (s_sin.c)
 static __host__ __device__ bool in_domain(int fn, float x)
@@ -86,6 +88,8 @@ __global__ void k_eval(int fn, uint64_t begin, uint32_t n, uint64_t* __restrict_
         case F_DPOW5: r = pow(d, 5.0); break;
         case F_DPOW15: r = pow(d, 1.5); break;
         case F_DPOW025: r = pow(d, 0.25); break;
+        case F_DPOW5FAST: r = pow5_d(d); break;
+        case F_DPOWQFAST: r = pow_quarter_d(d); break;
         default: r = (x >= -kErfLimit && x <= kErfLimit) ? (double)ptg::dm::inv_erf(x) : 0.0; break;
         }
         out[i] = __double_as_longlong(r);
@@ -133,6 +137,8 @@ static double host_eval(int fn, float x)
     case F_DPOW5: return pow(d, 5.0);
     case F_DPOW15: return pow(d, 1.5);
     case F_DPOW025: return pow(d, 0.25);
+    case F_DPOW5FAST: return pow(d, 5.0);
+    case F_DPOWQFAST: return pow(d, 0.25);
     default: return (x >= -kErfLimit && x <= kErfLimit) ? (double)host_inv_erf(x) : 0.0;
     }
 }
