@@ -50,12 +50,15 @@ struct DevScene {
 // PTG_DEBUG builds check every index the walks and the shading derive from
 // the records before they use it; a violation is counted in DevScene::debug
 // (slot below), the walk of that ray ends instead of reading out of bounds,
-// and the render returns PTG_E_RANGE naming the slot.
+// and the render returns PTG_E_RANGE naming the slot.  kDebugRound: a
+// wavefront kernel of round r loaded a path whose meta names another round
+// (dead lanes carry round 0 in every round) - its PathSoA half was
+// overwritten while still in use, e.g. by a camera kernel ordered too early.
 #ifndef PTG_DEBUG
 #define PTG_DEBUG 0
 #endif
 enum : uint32_t { kDebugNode = 0, kDebugTri = 1, kDebugInst = 2, kDebugQueue = 3, kDebugList = 4, kDebugStack = 5,
-                   kDebugSlots = 8 };
+                   kDebugRound = 6, kDebugSlots = 8 };
 
 // Aperture polygons with at most kPolyMaxSides sides read their vertex
 // directions from DevScene::polygon (k_polygon_table).

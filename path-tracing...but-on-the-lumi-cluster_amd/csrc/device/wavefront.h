@@ -52,6 +52,19 @@ PTG_D bool meta_nee(uint4 m) { return (m.y >> 8) & 1u; }
 PTG_D uint32_t meta_sub(uint4 m) { return m.y >> 16; }
 PTG_D uint32_t meta_pack(uint32_t round, bool nee, uint32_t sub) { return round | (nee ? 0x100u : 0u) | (sub << 16); }
 
+#if PTG_DEBUG
+// PTG_DEBUG: a wavefront kernel of round `round` loaded this path's meta.  The
+// round it names must be the kernel's own, else the kernel is reading a
+// PathSoA half that something else has overwritten (kDebugRound).  A dead lane
+// is queued by the camera alone and retires in round 0's sky kernel: it stands
+// for round 0 whatever its round bits say, and is a violation in any later round.
+PTG_D void debug_check_round(const DevScene& sc, uint4 meta, uint32_t round)
+{
+    const uint32_t r = (meta.y & META_DEAD) ? 0u : meta_round(meta);
+    if(r != round && sc.debug) atomicAdd(sc.debug + kDebugRound, 1u);
+}
+#endif
+
 // Append `active` lanes of the calling wave to a queue; one atomic per wave.
 __device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool active)
 {
@@ -167,7 +180,16 @@ template<bool COUNT, int KIND = 0, class MP = MathExact>
 PTG_D ShadeResult shade_path(const DevScene& sc, PathRec& p, const Hit& h, bool occluded, float4* out_samples,
                              Counters& cnt, MP& mp)
 {
-    if(p.meta.y & META_DEAD) return SH_DONE;
+    if(p.meta.y & META_DEAD)
+    {   // a lane of the chunk whose pixel is not live (a partial tile): its
+        // sample is zero.  Written here, not by the camera, which may run
+        // before the slot's previous chunk is folded.  A dead path always
+        // retires here from round 0's sky kernel (KIND 2): its root is kBePop,
+        // so its walk ends at the first step with thit = -1 and classify puts
+        // it on the sky list.  Lanes outside the chunk have no sample slot.
+        if(KIND == 2 && p.meta.x != 0xFFFFFFFFu) st_out(out_samples + p.meta.x, make_float4(0.f, 0.f, 0.f, 0.f));
+        return SH_DONE;
+    }
     const uint8_t* sf = sc.subframes + size_t(meta_sub(p.meta)) * SF_STRIDE;
     const Light L = light_of(sf);
     const uint32_t round = meta_round(p.meta);

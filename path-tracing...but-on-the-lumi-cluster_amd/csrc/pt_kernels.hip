@@ -200,10 +200,14 @@ __device__ __forceinline__ void chunk_coords(uint32_t i, uint32_t nj, uint32_t& 
 // counts[2r]: paths queued for round r; counts[2r+1]: their pending NEE rays.
 // Round 0 is every lane of the chunk in lane order (queue position = lane, no
 // compaction); lanes outside the chunk or the image are queued as dead paths
-// (an empty TLAS, retired by the first shade).
+// (an empty TLAS, retired by the first shade).  The camera writes path state
+// and counts[0] only, never the slot's sample buffer: a hoisted camera runs
+// before the fold of the chunk ahead of it has read that buffer
+// (trace_chunk_wavefront), so a dead lane's zero sample is written where the
+// dead path retires (shade_path).
 template<bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_wf_camera(DevScene sc, PixelMap pm, uint32_t j0, uint32_t nj, uint32_t M,
-                                                      PathSoA S, uint32_t* __restrict__ counts, float4* __restrict__ out,
+                                                      PathSoA S, uint32_t* __restrict__ counts,
                                                       unsigned long long* __restrict__ counters)
 {
     if(blockIdx.x == 0 && threadIdx.x == 0) counts[0] = M;
@@ -217,7 +221,6 @@ __global__ __launch_bounds__(kBlock) void k_wf_camera(DevScene sc, PixelMap pm, 
         const uint32_t slot = in_chunk ? jj * pm.npix + p : 0xFFFFFFFFu;
         if(!live)
         {
-            if(in_chunk) st_out(out + slot, make_float4(0.f, 0.f, 0.f, 0.f));
             st_state(S.meta + i, make_uint4(slot, META_DEAD, kBePop, 0u));   // no TLAS: the walk ends at once
             st_state(S.ray_o + i, make_float4(0.f, 0.f, 0.f, 0.f));
             st_state(S.ray_d + i, make_float4(0.f, 0.f, 1.f, 0.f));
@@ -273,20 +276,29 @@ constexpr uint32_t kCountWords(uint32_t rounds) { return 4 * (rounds + 2) + 2 * 
 // 4 B (2 NEE lists, hit, sky, redo); the chunk sizing budgets with it and
 // carve_slot_state checks it against the fields it hands out
 constexpr size_t kStateBytesPerPath = 2 * 9 * 16 + 2 * (16 + 8 + 4) + 5 * 4;
-// the path state of one chunk pipeline (ptg_context::Slot::state)
+// the path state of one chunk pipeline (ptg_context::Slot::state).  A chunk
+// whose round 0 reads half S[p] uses S[(p + r) & 1] as round r's `cur` and the
+// other half as its `nxt`; its last round appends no survivors, so the half
+// S[(p + rounds) & 1] is free once round `rounds - 2` has been shaded, and the
+// slot's next chunk takes it as its round-0 half: its camera kernel can run
+// beside this chunk's last round (trace_chunk_wavefront).  That camera also
+// zeroes and starts the next chunk's counters while this chunk's are in use,
+// hence two blocks of them, alternating per chunk.  TraceOut sets and NEE
+// lists go by the round's own parity: the camera touches neither.
 struct SlotState {
     PathSoA S[2];
     TraceOut trs[2];   // per round parity: the sky kernel of round r reads its set while round r+1 writes the other
     uint32_t* lists[2];                 // NEE lists, by round parity
     uint32_t *hit_list, *sky_list;      // this round's paths by shading kernel
     uint32_t* redo_hit;                 // surface paths to shade again with MathExact
-    uint32_t* counts;                   // kCountWords(rounds) words
+    uint32_t* counts[2];                // kCountWords(rounds) words each, by chunk parity on the slot
 };
-constexpr size_t slot_state_bytes(size_t M, uint32_t rounds) { return M * kStateBytesPerPath + kCountWords(rounds) * 4 + 256; }
+constexpr size_t slot_state_bytes(size_t M, uint32_t rounds) { return M * kStateBytesPerPath + 2 * kCountWords(rounds) * 4 + 256; }
 // Cuts a slot's state buffer (slot_state_bytes(M, rounds) at `base`) into its
-// arrays of M entries, in this order in memory, the counts behind them.
+// arrays of M entries, in this order in memory, the two counts blocks behind
+// them (kCountWords is even: both stay 8-byte aligned for the packed atomics).
 // False if the fields' bytes per path are not kStateBytesPerPath.
-inline bool carve_slot_state(char* base, size_t M, SlotState& t)
+inline bool carve_slot_state(char* base, size_t M, uint32_t rounds, SlotState& t)
 {
     size_t per_path = 0;
     auto take = [&](auto*& field) {
@@ -301,7 +313,8 @@ inline bool carve_slot_state(char* base, size_t M, SlotState& t)
     }
     for(TraceOut& o: t.trs) { take(o.hit); take(o.bary); take(o.shadow); }
     take(t.lists[0]); take(t.lists[1]); take(t.hit_list); take(t.sky_list); take(t.redo_hit);
-    t.counts = reinterpret_cast<uint32_t*>(base + per_path * M);
+    t.counts[0] = reinterpret_cast<uint32_t*>(base + per_path * M);
+    t.counts[1] = t.counts[0] + kCountWords(rounds);
     return per_path == kStateBytesPerPath;
 }
 constexpr uint32_t kRedoGrid = 16;   // blocks of the MathExact shading passes (grid-stride over a short list)
@@ -420,6 +433,9 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
                         {
                             // path state streams once through the caches: non-temporal
                             const uint4 m = nt_load(S.meta + q);
+#if PTG_DEBUG
+                            debug_check_round(sc, m, round);
+#endif
                             w.init(m.z, xyz(nt_load(S.ray_o + q)),
                                    ANY ? xyz(nt_load(S.nee_d + q)) : xyz(nt_load(S.ray_d + q)), tmin, tmax);
                             if(ANY) w.try_candidate(sc, occ_inst, occ_prim, meta_sub(m));
@@ -641,6 +657,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MP::kFas
             bool occluded;
             const uint32_t q = hit_list[i];
             load_queued(cur, tr, q, p, h, occluded, round > 0);
+#if PTG_DEBUG
+            debug_check_round(sc, p.meta, round);
+#endif
             MP mp = mp0;
             const ShadeResult res = shade_path<COUNT, 1, MP>(sc, p, h, occluded, out, cnt, mp);
             if(MP::kFast && res == SH_REDO)
@@ -708,6 +727,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PTG_SKY_
         Hit h;
         bool occluded;
         load_queued<true>(cur, tr, sky_list[i], p, h, occluded, round > 0);
+#if PTG_DEBUG
+        debug_check_round(sc, p.meta, round);
+#endif
         shade_path<COUNT, 2>(sc, p, h, occluded, out, cnt, mp);
     }
     if(COUNT) flush_counters(cnt, counters, 0);
@@ -1336,13 +1358,13 @@ __global__ __launch_bounds__(kBlock) void k_ad_select(uint32_t w, uint32_t h, ui
 }
 
 // k_wf_camera over a pixel list with the pass's strided sample map: queue
-// position, PathSoA records, dead lanes and out[slot] exactly as k_wf_camera
-// writes them for a map of ad.len pixels (chunk_coords: 8 list entries x 8
-// local samples per wave), so the walk, classify, shade and sky kernels run
-// on its queue unchanged.
+// position, PathSoA records and dead lanes exactly as k_wf_camera writes them
+// for a map of ad.len pixels (chunk_coords: 8 list entries x 8 local samples
+// per wave), so the walk, classify, shade and sky kernels run on its queue
+// unchanged.
 template<bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_ad_camera(DevScene sc, AdaptivePass ad, uint32_t j0, uint32_t nj, uint32_t M,
-                                                      PathSoA S, uint32_t* __restrict__ counts, float4* __restrict__ out,
+                                                      PathSoA S, uint32_t* __restrict__ counts,
                                                       unsigned long long* __restrict__ counters)
 {
     if(blockIdx.x == 0 && threadIdx.x == 0) counts[0] = M;
@@ -1356,7 +1378,6 @@ __global__ __launch_bounds__(kBlock) void k_ad_camera(DevScene sc, AdaptivePass 
         const uint32_t slot = in_chunk ? jj * ad.len + p : 0xFFFFFFFFu;
         if(!in_chunk || pix >= ad.w * ad.h)
         {
-            if(in_chunk) st_out(out + slot, make_float4(0.f, 0.f, 0.f, 0.f));
             st_state(S.meta + i, make_uint4(slot, META_DEAD, kBePop, 0u));   // no TLAS: the walk ends at once
             st_state(S.ray_o + i, make_float4(0.f, 0.f, 0.f, 0.f));
             st_state(S.ray_d + i, make_float4(0.f, 0.f, 1.f, 0.f));
@@ -1572,9 +1593,10 @@ struct ptg_context {
     // its chunk's slot stream, chained by events across the slots (fold_chunk).
     // The megakernel and concurrency levels 0 / 1 use slot 0 alone.
     struct Slot {
-        // main: camera, closest-hit walk, classify, shade, fold; side: shadow
-        // walk and sky.  Slot 0 has no main stream of its own: its chunks run
-        // on the caller's stream (main_of)
+        // main: the slot's first camera, closest-hit walk, classify, shade,
+        // fold; side: shadow walk, sky and the camera of the slot's next chunk
+        // (trace_chunk_wavefront).  Slot 0 has no main stream of its own: its
+        // chunks run on the caller's stream (main_of)
         hipStream_t main = nullptr, side = nullptr;
         // the events that order main and side; ev_acc: the slot's last fold done
         hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_acc = nullptr;
@@ -1584,6 +1606,7 @@ struct ptg_context {
     hipStream_t main_of(uint32_t k) const { return k ? slot[k].main : stream; }
     uint32_t concurrency = 2;              // ptg_set_concurrency
     hipEvent_t ev_render_start = nullptr;
+    hipEvent_t ev_first_camera = nullptr;  // a render's first camera kernels take turns (trace_chunk_wavefront)
     ~ptg_context()
     {
         for(Slot& b: slot)
@@ -1594,6 +1617,7 @@ struct ptg_context {
                 if(st) (void)hipStreamDestroy(st);
         }
         if(ev_render_start) (void)hipEventDestroy(ev_render_start);
+        if(ev_first_camera) (void)hipEventDestroy(ev_first_camera);
         for(hipEvent_t e: ev_start) (void)hipEventDestroy(e);
         for(hipEvent_t e: ev_stop) (void)hipEventDestroy(e);
     }
@@ -1765,6 +1789,13 @@ struct RenderJob {
     uint32_t prev_slot = 0xFFFFFFFFu;      // the slot of the last fold
     float4* out_moments = nullptr;         // ptg_render_moments: the fold also keeps the luminance moments
     SlotState st[kWfSlots];
+    // where a slot's next wavefront chunk stands (trace_chunk_wavefront)
+    struct Cursor {
+        uint32_t parity = 0;               // the PathSoA half of its round 0
+        uint32_t chunks = 0;               // chunks traced on the slot so far: chunk k counts in block k & 1
+        bool camera_queued = false;        // its camera kernel was hoisted into the chunk before it
+    } cursor[kWfSlots];
+    bool first_camera_queued = false;      // ctx->ev_first_camera is recorded in this render
 
     unsigned long long* cnt_for(int kind) const { return cnt ? cnt + 8 * kind : nullptr; }
     unsigned long long* ws_for(bool any) const { return cnt ? cnt + 8 * K_KINDS + (any ? WS_COUNT : 0) : nullptr; }
@@ -1841,15 +1872,60 @@ int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
 // previous round's NEE rays, classify, shade and sky.  With `ad` (a pass of
 // render_adaptive) the camera kernel is k_ad_camera over the pass's pixel
 // list, pc.j counting the pass's local samples; everything after it is the same.
-int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const AdaptivePass* ad = nullptr)
+//
+// The hoisted camera.  `next` is the slot's next chunk of this render (null:
+// none).  With a side stream (concurrency >= 1) its camera kernel is queued
+// here, on the side stream inside this chunk's last round, so it runs beside
+// that round's walk, classify and shade and beside the other slot's kernels,
+// instead of alone between two chunks where nothing else of the slot can run
+// (profiles/r06c_timeline/: both slots' cameras met there twice a frame).
+// What it writes, and why nothing still in use:
+//   - the PathSoA half S[(p + rounds) & 1] (SlotState).  Its last readers are
+//     round `rounds - 2`'s extend, shadow, shade (which reads `cur`) and sky.
+//     That sky kernel is ahead of the camera on the side stream, and it was
+//     queued behind an event recorded on main after that round's shade, so
+//     the main stream's readers are done as well.  With rounds < 2 the last
+//     readers are the same kernels of the slot's chunk before this one, and
+//     the same argument holds with that chunk's sky kernel.  The last round's
+//     shade writes no survivor into the half (shade_path retires every path
+//     at round == max_bounces).
+//   - the other counts block, zeroed first on the same stream.  Its last user
+//     is the chunk before this one, whose last sky kernel is ahead on the
+//     side stream, behind its last shade.
+//   - nothing else: not the sample buffer, which this chunk's fold has yet to
+//     read (dead lanes: shade_path), neither TraceOut set, no list.
+// The side stream also waits here for what main has queued so far: in a
+// render's first chunk with rounds < 2 nothing else orders it behind the
+// caller's upload of the frame the camera reads.
+// What reads the camera's output, the next chunk's round 0 on main, is behind
+// this chunk's closing join of the side stream.  The hoist adds no event: the
+// slot's two are each recorded and waited for in one step, record first (the
+// two lambdas below), so no wait can meet an event that is recorded later in
+// submission order, which HIP would take as satisfied (the first cameras'
+// event: see where it is used).
+// On the side stream it stands behind the last round's shadow walk and the
+// event classify waits for, and ahead of that round's sky kernel (ahead of
+// the shadow walk, classify and shade wait for it too: measured slower,
+// DESIGN 4.16).  Timing knobs, the frames do not depend on them:
+// PTG_HOIST_CAMERA = 0 keeps every camera in order on main,
+// PTG_CAMERAS_IN_TURN = 0 starts a render's first cameras side by side (below).
+#ifndef PTG_HOIST_CAMERA
+#define PTG_HOIST_CAMERA 1
+#endif
+#ifndef PTG_CAMERAS_IN_TURN
+#define PTG_CAMERAS_IN_TURN 1
+#endif
+int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = nullptr, const AdaptivePass* ad = nullptr)
 {
     ptg_context* ctx = job.ctx;
     ptg_context::Slot& sl = ctx->slot[pc.slot];
     const SlotState& t = job.st[pc.slot];
+    RenderJob::Cursor& at = job.cursor[pc.slot];
     const DevScene& sc = job.sc;
     const DevScene sc_ext = job.walk_scene(pc.slot, 0), sc_sh = job.walk_scene(pc.slot, 1);
     const uint32_t rounds = job.rounds;
-    uint32_t* counts = t.counts;
+    const uint32_t p = at.parity;
+    uint32_t* counts = t.counts[at.chunks & 1];
     const hipStream_t ms = ctx->main_of(pc.slot);
     // second stream: the previous round's sky kernel, then this round's
     // shadow walk (independent of the closest-hit walk it runs beside)
@@ -1866,22 +1942,54 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const AdaptivePass* a
         PTG_HIP(hipStreamWaitEvent(ms, sl.ev_side, 0));
         return PTG_OK;
     };
-    const size_t lanes = job.lanes(pc.n);
+    auto grid_of = [&](const Piece& c) {
+        return dim3(std::max<uint32_t>(1, std::min<uint32_t>(ctx->persistent_blocks, grid_for(job.lanes(c.n)))));
+    };
+    // chunk c's camera on stream st: zeroes counts block `cb` and fills half `half`
+    auto camera = [&](const Piece& c, hipStream_t st, uint32_t half, uint32_t* cb) -> int {
+        const uint32_t M = uint32_t(job.lanes(c.n));
+        PTG_HIP(hipMemsetAsync(cb, 0, kCountWords(rounds) * sizeof(uint32_t), st));
+        return ad ? launch(ctx, K_CAMERA, st, grid_of(c), 0, k_ad_camera<true>, k_ad_camera<false>, sc, *ad, c.j, c.n, M,
+                           t.S[half], cb, job.cnt_for(K_CAMERA))
+                  : launch(ctx, K_CAMERA, st, grid_of(c), 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, c.j, c.n, M,
+                           t.S[half], cb, job.cnt_for(K_CAMERA));
+    };
     float4* out = sl.samples.as<float4>();
-    PTG_HIP(hipMemsetAsync(counts, 0, kCountWords(rounds) * sizeof(uint32_t), ms));
-    const dim3 grid(std::max<uint32_t>(1, std::min<uint32_t>(ctx->persistent_blocks, grid_for(lanes))));
-    if(int e = ad ? launch(ctx, K_CAMERA, ms, grid, 0, k_ad_camera<true>, k_ad_camera<false>, sc, *ad, pc.j, pc.n,
-                           uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA))
-                  : launch(ctx, K_CAMERA, ms, grid, 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, pc.j, pc.n,
-                           uint32_t(lanes), t.S[0], counts, out, job.cnt_for(K_CAMERA)))
-        return e;
+    const dim3 grid = grid_of(pc);
+    if(!at.camera_queued)
+    {
+        // The first cameras of a render take turns (concurrency 2): side by
+        // side they take twice as long and no walk can start before one is
+        // done, so slot k's waits for slot k - 1's, and slot 0's round-0 walk
+        // starts after one camera's time with slot 1's camera beside it.  The
+        // chunk plan deals a render's first chunks to slots 0, 1, ... in that
+        // order, so the event is recorded before it is waited for, and
+        // recorded again behind the camera that waited.
+        const bool in_turn = PTG_CAMERAS_IN_TURN && job.pipelines > 1 && at.chunks == 0 && !ad;
+        if(in_turn && job.first_camera_queued) PTG_HIP(hipStreamWaitEvent(ms, ctx->ev_first_camera, 0));
+        if(int e = camera(pc, ms, p, counts)) return e;
+        if(in_turn)
+        {
+            PTG_HIP(hipEventRecord(ctx->ev_first_camera, ms));
+            job.first_camera_queued = true;
+        }
+    }
+    // the slot's next chunk: the half and the counts block this one leaves free
+    const bool hoist = PTG_HOIST_CAMERA && next && job.overlap && !ad;
+    at.parity = (p + rounds) & 1;
+    at.chunks += 1;
+    at.camera_queued = hoist;
+    auto hoisted_camera = [&]() -> int { return camera(*next, sl.side, at.parity, t.counts[at.chunks & 1]); };
     for(uint32_t r = 0; r < rounds; ++r)
     {
-        const PathSoA& cur = t.S[r & 1];
-        const PathSoA& nxt = t.S[(r + 1) & 1];
+        const PathSoA& cur = t.S[(p + r) & 1];
+        const PathSoA& nxt = t.S[(p + r + 1) & 1];
+        const bool last = r + 1 == rounds;
         const TraceOut& tr = t.trs[r & 1];
         uint32_t* nee_next = t.lists[(r + 1) & 1];
         uint32_t* shadow_next = t.trs[(r + 1) & 1].shadow;
+        if(hoist && last)
+            if(int e = side_after_main()) return e;   // before this round's walk is queued: the camera is not to wait for it
         if(int e = launch(ctx, K_EXTEND, ms, ctx->walk_grid[0], ctx->walk_lds[0], k_wf_walk<false, true>,
                           k_wf_walk<false, false>, sc_ext, cur, counts, r, nullptr, tr, ctx->walk_xcds[0],
                           job.cnt_for(K_EXTEND), job.ws_for(false)))
@@ -1896,6 +2004,11 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const AdaptivePass* a
         // classify/shade need the shadow results, the lists the previous sky
         // kernel read, and the state set it read
         if(int e = main_after_side()) return e;
+        // the slot's next camera, behind the event classify waits for: it runs
+        // beside the rest of this round's walk, classify and shade, and only
+        // this round's sky kernel and the fold wait for it
+        if(hoist && last)
+            if(int e = hoisted_camera()) return e;
         if(int e = launch(ctx, K_CLASSIFY, ms, grid, 0, k_wf_classify, k_wf_classify, counts, r, tr, t.hit_list, t.sky_list, lc))
             return e;
         // the certified pass, then the exact pass over the paths it listed: one timed interval
@@ -1951,7 +2064,7 @@ int fold_chunk(RenderJob& job, const Piece& pc)
 }
 
 #if PTG_DEBUG
-// PTG_DEBUG builds: the render's out-of-range index tallies (waits for the render)
+// PTG_DEBUG builds: the render's violation tallies, layout.h's kDebug* slots (waits for the render)
 int check_debug_tallies(ptg_context* ctx)
 {
     uint32_t dbg[kDebugSlots];
@@ -1960,7 +2073,10 @@ int check_debug_tallies(ptg_context* ctx)
     std::string bad;
     static const char* names[kDebugSlots] = {"node record", "triangle", "instance", "NEE list", "shade list", "walk stack", "", ""};
     for(uint32_t k = 0; k < kDebugSlots; ++k)
-        if(dbg[k]) bad += std::string(bad.empty() ? "" : ", ") + names[k] + " index out of range x" + std::to_string(dbg[k]);
+        if(dbg[k])
+            bad += std::string(bad.empty() ? "" : ", ") +
+                   (k == kDebugRound ? std::string("path state of another round loaded") : std::string(names[k]) + " index out of range") +
+                   " x" + std::to_string(dbg[k]);
     if(bad.empty()) return PTG_OK;
     PTG_HIP(hipMemset(ctx->debug.p, 0, sizeof(dbg)));
     return fail(PTG_E_RANGE, "PTG_DEBUG: " + bad);
@@ -2022,7 +2138,7 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
         for(uint32_t k = 0; k < pipelines; ++k)
         {
             PTG_HIP(ctx->grow(ctx->slot[k].state, slot_state_bytes(job.M, job.rounds)));
-            if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.st[k]))
+            if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.rounds, job.st[k]))
                 return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
         }
     if(pipelines > 1)
@@ -2034,9 +2150,12 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
     job.sc = ctx->scene_args(cfg);
     job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
     if(wf) PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * pipelines * job.spill_region) * sizeof(uint2)));
-    for(const Piece& pc: plan_chunks(job))
+    const std::vector<Piece> plan = plan_chunks(job);
+    for(size_t k = 0; k < plan.size(); ++k)
     {
-        if(int r = wf ? trace_chunk_wavefront(job, pc) : trace_chunk_megakernel(job, pc)) return r;
+        const Piece& pc = plan[k];
+        const Piece* next = k + pipelines < plan.size() ? &plan[k + pipelines] : nullptr;   // the slot's next chunk
+        if(int r = wf ? trace_chunk_wavefront(job, pc, next) : trace_chunk_megakernel(job, pc)) return r;
         if(int r = fold_chunk(job, pc)) return r;
     }
     if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
@@ -2129,13 +2248,13 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
         {
             PTG_HIP(ctx->grow(ctx->slot[s].samples, size_t(len) * job.chunk * sizeof(float4)));
             PTG_HIP(ctx->grow(ctx->slot[s].state, slot_state_bytes(job.M, job.rounds)));
-            if(!carve_slot_state(ctx->slot[s].state.as<char>(), job.M, job.st[s]))
+            if(!carve_slot_state(ctx->slot[s].state.as<char>(), job.M, job.rounds, job.st[s]))
                 return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
         }
         const AdaptivePass ad{rect.x0, rect.y0, rect.w, rect.h, P.passes, k, cfg->samples_per_motion_blur_step, list, len};
         for(const Piece& pc: plan_chunks(job))
         {
-            if(int r = trace_chunk_wavefront(job, pc, &ad)) return r;
+            if(int r = trace_chunk_wavefront(job, pc, nullptr, &ad)) return r;
             if(int r = fold_chunk_adaptive(job, pc, ad)) return r;
         }
         if(k + 1 < P.min_passes || k + 1 >= P.passes) continue;
@@ -2278,6 +2397,7 @@ int ptg_context_create(int device, ptg_context** out)
             PTG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     PTG_HIP(hipEventCreateWithFlags(&ctx->ev_render_start, hipEventDisableTiming));
+    PTG_HIP(hipEventCreateWithFlags(&ctx->ev_first_camera, hipEventDisableTiming));
     *out = ctx.release();
     return PTG_OK;
 }
