@@ -405,6 +405,56 @@ int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_
                             const ptg_float4* hist_albedo, const ptg_float4* hist_normal_depth,
                             ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra);
 
+/* ---- temporal accumulation: several cameras and a history clamp -----------
+ * ptg_temporal_accumulate with two insertions, for a frame whose camera moves
+ * (DESIGN.md 4.17 is the definition; denoise.temporal_clamped_reference the
+ * CPU restatement, bit for bit).
+ *  - The reprojection runs once per camera of `cams`, in order, with the
+ *    same pixel, depth and hist_cam; every valid tap of every camera adds into
+ *    the same sums, and a camera that fails a test adds nothing.  Passing the
+ *    subframe cameras of a motion-blurred frame gathers the history along the
+ *    blur.  n_cams == 1 is ptg_temporal_accumulate's reprojection exactly.
+ *  - With clamp_radius r > 0, a pixel that found history has the history's
+ *    colour clamped per channel to [mu - clamp_sigma * sd, mu + clamp_sigma *
+ *    sd], mu and sd the mean and standard deviation of this frame's radiance
+ *    over the (2r + 1)^2 window around the pixel (pixels outside the image or
+ *    with a non-finite channel left out; an empty window does not clamp).
+ *    Where a channel was clipped, the history's first luminance moment moves
+ *    with the colour, the second keeps the variance, and the history's sample
+ *    count is capped at clipped_history (before the max_history cap).
+ * With n_cams == 1 and clamp_radius == 0 the outputs are
+ * ptg_temporal_accumulate's bits. */
+typedef struct {
+    ptg_temporal_params base;   /* as for ptg_temporal_accumulate */
+    uint32_t clamp_radius;      /* 0: no clamp; 1 or 2: window (2r+1)^2 of this frame's radiance */
+    float clamp_sigma;          /* half-width of the colour box, in standard deviations of the window */
+    float clipped_history;      /* cap on the history's sample count at a pixel whose history was clipped */
+} ptg_temporal_clamp_params;
+/* base: ptg_temporal_params_default's; clamp_radius 1, clamp_sigma 2,
+ * clipped_history 32: the best row of the measured sweep. */
+void ptg_temporal_clamp_params_default(ptg_temporal_clamp_params* params);
+/* The image arguments, hist_cam and everything ptg_temporal_accumulate says
+ * about them carry over: the all-or-nothing history, no output that is a
+ * hist_* image, out_radiance != out_moments, PTG_E_RANGE above 2^24.  Beyond
+ * that: cams is a HOST array of n_cams cameras, 1 <= n_cams <= 512, read
+ * before the call returns (they travel through a buffer the context owns; a
+ * call queued behind another does not disturb it); clamp_radius <= 2;
+ * clamp_sigma and clipped_history positive and finite; anything else is
+ * PTG_E_INVALID and launches nothing.  With clamp_radius > 0 the radiance is
+ * gathered from neighbours, so out_radiance == radiance is PTG_E_INVALID;
+ * with clamp_radius == 0 it stays allowed, and out_moments == moments is
+ * allowed in both cases (the moments are read at the pixel alone).
+ * out_flags (optional, DEVICE, [h][w] bytes): bit 0 the pixel found history,
+ * bit 1 its history was clipped.  Asynchronous on the context's stream. */
+int ptg_temporal_accumulate_clamped(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_clamp_params* params,
+                                    uint32_t n_cams, const ptg_camera* cams, const ptg_camera* hist_cam,
+                                    const ptg_float4* radiance, const ptg_float4* moments,
+                                    const ptg_float4* albedo, const ptg_float4* normal_depth,
+                                    const ptg_float4* hist_radiance, const ptg_float4* hist_moments,
+                                    const ptg_float4* hist_albedo, const ptg_float4* hist_normal_depth,
+                                    ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra,
+                                    uint8_t* out_flags);
+
 /* ---- adaptive sampling ----------------------------------------------------
  * A render that stops sampling a pixel once its mean is known well enough.
  * cfg->samples_per_pixel = N is the budget (the frame is set up for it: N / m

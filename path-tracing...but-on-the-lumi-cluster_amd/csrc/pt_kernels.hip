@@ -17,6 +17,8 @@
 //                   or DenoiseGuidedStep (variance-guided)
 //   k_temporal_accumulate  last frame's radiance and moments, reprojected
 //                   and blended with this frame's by sample count
+//   k_temporal_accumulate_clamped  the same through a list of cameras, the
+//                   history clamped to the frame's local colour range
 //   k_ad_select<ALL>, k_ad_camera, k_ad_fold, k_ad_resolve
 //                   adaptive sampling (ptg_render_adaptive): the stopping rule
 //                   compacted into a pixel list, the camera kernel and the
@@ -1160,6 +1162,105 @@ __device__ __forceinline__ float tp_var_of_mean(float m1, float m2, float n)
     return n >= 2.0f ? var / (n - 1.0f) : 0.0f;
 }
 
+// Steps 2-4 of the definition for one camera: the first-hit point of pixel
+// (x, y), from its centre ray through `cam` and the mean depth z, is
+// projected into `hist`; the four bilinear taps around it that show the same
+// surface (depth, normal, albedo) add into the seven running sums.  A camera
+// that fails a test adds nothing.  One definition for both kernels below.
+struct TemporalSums {
+    float sw = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
+};
+__device__ __forceinline__ void tp_gather(TemporalSums& s, uint32_t w, uint32_t h, float depth_tolerance,
+                                          float normal_tolerance, float albedo_tolerance, const TemporalCam& cam,
+                                          const TemporalCam& hist, uint32_t x, uint32_t y, float z, const float4& A,
+                                          const float4& G, const float4* __restrict__ hist_radiance,
+                                          const float4* __restrict__ hist_moments, const float4* __restrict__ hist_albedo,
+                                          const float4* __restrict__ hist_normal_depth)
+{
+    const float uvx = (((float)x + 0.5f) / (float)w * 2.0f - 1.0f) * cam.aspect;
+    const float uvy = -(((float)y + 0.5f) / (float)h * 2.0f - 1.0f);
+    const f3 d = normalize(V3(uvx * cam.ifl * cam.fd, uvy * cam.ifl * cam.fd, -1.0f * cam.fd));
+    const f3 dir = mul_m3v3(cam.ori, d);
+    const f3 P = cam.pos + dir * z;
+    const f3 q = P - hist.pos;
+    const f3 l = mul_v3m3(q, hist.ori);
+    if(l.z < 0.0f)
+    {
+        const float t = -l.z;
+        const float sx = (l.x / t) / hist.ifl / hist.aspect;
+        const float sy = -((l.y / t) / hist.ifl);
+        const float fx = (sx + 1.0f) * 0.5f * (float)w - 0.5f;
+        const float fy = (sy + 1.0f) * 0.5f * (float)h - 0.5f;
+        const float ze = fsqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
+        if(__builtin_isfinite(fx) && __builtin_isfinite(fy))
+        {
+            const float ix = floorf(fx), iy = floorf(fy);
+            const float tx = fx - ix, ty = fy - iy;
+            const float xmax = (float)(w - 1u), ymax = (float)(h - 1u);
+#pragma unroll
+            for(int b = 0; b < 2; ++b)
+            {
+                const float Y = iy + (float)b;
+                const float wy = b ? ty : 1.0f - ty;
+#pragma unroll
+                for(int c = 0; c < 2; ++c)
+                {
+                    const float X = ix + (float)c;
+                    const float bw = (c ? tx : 1.0f - tx) * wy;
+                    // inside on the floats; an integer only after that
+                    if(!(X >= 0.0f && X <= xmax && Y >= 0.0f && Y <= ymax)) continue;
+                    const size_t t4 = size_t((uint32_t)Y) * w + size_t((uint32_t)X);
+                    const float4 HA = hist_albedo[t4];
+                    if(!(HA.w > 0.0f)) continue;
+                    const float4 H = hist_radiance[t4];
+                    if(!finite3(V3(H.x, H.y, H.z))) continue;
+                    const float4 HM = hist_moments[t4];
+                    if(!(HM.w > 0.0f)) continue;
+                    const float4 HG = hist_normal_depth[t4];
+                    const float zh = HG.w / HA.w;
+                    const float zm = zh > ze ? zh : ze;
+                    if(!(fabsf(zh - ze) <= depth_tolerance * zm)) continue;
+                    const float nx = G.x - HG.x, ny = G.y - HG.y, nz = G.z - HG.z;
+                    const float dn = (nx * nx + ny * ny) + nz * nz;
+                    if(!(dn <= normal_tolerance)) continue;
+                    const float ax = A.x - HA.x, ay = A.y - HA.y, az = A.z - HA.z, aw = A.w - HA.w;
+                    const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
+                    if(!(da <= albedo_tolerance)) continue;
+                    s.sw = s.sw + bw;
+                    s.cx = s.cx + bw * H.x;
+                    s.cy = s.cy + bw * H.y;
+                    s.cz = s.cz + bw * H.z;
+                    s.s1 = s.s1 + bw * HM.x;
+                    s.s2 = s.s2 + bw * HM.y;
+                    s.sn = s.sn + bw * HM.w;
+                }
+            }
+        }
+    }
+}
+
+// Steps 6-7: the history (hx, hy, hz; h1, h2; hn samples, not yet capped at
+// max_history) blended with this frame's R and M by their sample counts, or
+// the history alone where this frame brings nothing usable.
+__device__ __forceinline__ void tp_blend(float hx, float hy, float hz, float h1, float h2, float hn, float max_history,
+                                         const float4& R, const float4& M, float4& oc, float4& om)
+{
+    const float nh = hn < max_history ? hn : max_history;
+    if(finite3(V3(R.x, R.y, R.z)) && M.w > 0.0f)
+    {
+        const float nt = nh + M.w;
+        const float al = M.w / nt;
+        oc = make_float4(hx + al * (R.x - hx), hy + al * (R.y - hy), hz + al * (R.z - hz), 0.0f);
+        const float m1 = h1 + al * (M.x - h1), m2 = h2 + al * (M.y - h2);
+        om = make_float4(m1, m2, tp_var_of_mean(m1, m2, nt), nt);
+    }
+    else
+    {   // nothing usable in this frame: the history alone
+        oc = make_float4(hx, hy, hz, 0.0f);
+        om = make_float4(h1, h2, tp_var_of_mean(h1, h2, nh), nh);
+    }
+}
+
 // One work-item per pixel: the pixel's first-hit point, from its centre ray
 // through `cam` and its mean depth, is projected into `hist`; the four
 // bilinear taps around it that show the same surface (depth, normal, albedo)
@@ -1182,95 +1283,123 @@ __global__ __launch_bounds__(kBlock) void k_temporal_accumulate(TemporalArgs a, 
     if(i >= a.w * a.h) return;
     const uint32_t x = i % a.w, y = i / a.w;
     const float4 R = radiance[i], M = moments[i], A = albedo[i], G = normal_depth[i];
-    float sw = 0.0f, scx = 0.0f, scy = 0.0f, scz = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
+    TemporalSums s;
+    const float cov = A.w;
+    if(a.has_history && cov > 0.0f)
+        tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, a.cam, a.hist, x, y, G.w / cov, A, G,
+                  hist_radiance, hist_moments, hist_albedo, hist_normal_depth);
+    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
+    if(s.sw > 0.0f)
+        tp_blend(s.cx / s.sw, s.cy / s.sw, s.cz / s.sw, s.s1 / s.sw, s.s2 / s.sw, s.sn / s.sw, a.max_history, R, M, oc, om);
+    out_radiance[i] = oc;
+    out_moments[i] = om;
+    if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
+}
+
+// ---- temporal accumulation over several cameras, with a history clamp ----
+
+constexpr uint32_t kTemporalMaxCams = 512;  // ptg_temporal_accumulate_clamped's n_cams
+struct TemporalClampArgs {
+    uint32_t w, h;
+    uint32_t has_history;                  // 0: first frame, the hist_* pointers are null
+    uint32_t n_cams;                       // this frame's cameras, in the context's buffer
+    uint32_t clamp_radius;                 // 0: no clamp
+    float max_history, depth_tolerance, normal_tolerance, albedo_tolerance;
+    float clamp_sigma, clipped_history;
+    TemporalCam hist;
+};
+
+// k_temporal_accumulate with two insertions.  The reprojection runs once per
+// camera of `cams` (a wave-uniform loop: the cameras come through scalar
+// loads) into the same seven sums, so the history of a motion-blurred pixel is
+// gathered along the blur.  With clamp_radius r > 0 the history's colour is
+// then clamped, per channel, to mean +- clamp_sigma standard deviations of the
+// finite pixels of this frame's (2r + 1)^2 window; a clipped history's first
+// moment follows the colour, its second keeps the variance, and its sample
+// count is capped at clipped_history.  `radiance` is gathered by the clamp:
+// with r > 0 it is not out_radiance (the host refuses that).  flags
+// (optional): bit 0 the pixel found history, bit 1 its history was clipped.
+__global__ __launch_bounds__(kBlock) void k_temporal_accumulate_clamped(
+    TemporalClampArgs a, const TemporalCam* __restrict__ cams, const float4* radiance, const float4* moments,
+    const float4* __restrict__ albedo, const float4* __restrict__ normal_depth, const float4* __restrict__ hist_radiance,
+    const float4* __restrict__ hist_moments, const float4* __restrict__ hist_albedo,
+    const float4* __restrict__ hist_normal_depth, float4* out_radiance, float4* out_moments, uchar4* __restrict__ out_bgra,
+    uint8_t* __restrict__ flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= a.w * a.h) return;
+    const uint32_t x = i % a.w, y = i / a.w;
+    const float4 R = radiance[i], M = moments[i], A = albedo[i], G = normal_depth[i];
+    TemporalSums s;
     const float cov = A.w;
     if(a.has_history && cov > 0.0f)
     {
         const float z = G.w / cov;
-        const float uvx = (((float)x + 0.5f) / (float)a.w * 2.0f - 1.0f) * a.cam.aspect;
-        const float uvy = -(((float)y + 0.5f) / (float)a.h * 2.0f - 1.0f);
-        const f3 d = normalize(V3(uvx * a.cam.ifl * a.cam.fd, uvy * a.cam.ifl * a.cam.fd, -1.0f * a.cam.fd));
-        const f3 dir = mul_m3v3(a.cam.ori, d);
-        const f3 P = a.cam.pos + dir * z;
-        const f3 q = P - a.hist.pos;
-        const f3 l = mul_v3m3(q, a.hist.ori);
-        if(l.z < 0.0f)
+        for(uint32_t k = 0; k < a.n_cams; ++k)
+            tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, cams[k], a.hist, x, y, z, A, G,
+                      hist_radiance, hist_moments, hist_albedo, hist_normal_depth);
+    }
+    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
+    uint32_t fl = 0;
+    if(s.sw > 0.0f)
+    {
+        fl = 1u;
+        float hc[3] = {s.cx / s.sw, s.cy / s.sw, s.cz / s.sw};
+        float h1 = s.s1 / s.sw, h2 = s.s2 / s.sw, hn = s.sn / s.sw;
+        if(a.clamp_radius)
         {
-            const float t = -l.z;
-            const float sx = (l.x / t) / a.hist.ifl / a.hist.aspect;
-            const float sy = -((l.y / t) / a.hist.ifl);
-            const float fx = (sx + 1.0f) * 0.5f * (float)a.w - 0.5f;
-            const float fy = (sy + 1.0f) * 0.5f * (float)a.h - 0.5f;
-            const float ze = fsqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
-            if(__builtin_isfinite(fx) && __builtin_isfinite(fy))
+            const int32_t r = (int32_t)a.clamp_radius;
+            int32_t n = 0;
+            float su[3] = {0.0f, 0.0f, 0.0f}, sq[3] = {0.0f, 0.0f, 0.0f};
+            for(int32_t dy = -r; dy <= r; ++dy)
             {
-                const float ix = floorf(fx), iy = floorf(fy);
-                const float tx = fx - ix, ty = fy - iy;
-                const float xmax = (float)(a.w - 1u), ymax = (float)(a.h - 1u);
-#pragma unroll
-                for(int b = 0; b < 2; ++b)
+                const int32_t qy = (int32_t)y + dy;
+                if(qy < 0 || qy >= (int32_t)a.h) continue;
+                for(int32_t dx = -r; dx <= r; ++dx)
                 {
-                    const float Y = iy + (float)b;
-                    const float wy = b ? ty : 1.0f - ty;
+                    const int32_t qx = (int32_t)x + dx;
+                    if(qx < 0 || qx >= (int32_t)a.w) continue;
+                    const float4 Rq = radiance[size_t(qy) * a.w + size_t(qx)];
+                    if(!finite3(V3(Rq.x, Rq.y, Rq.z))) continue;
+                    ++n;
+                    su[0] = su[0] + Rq.x; sq[0] = sq[0] + Rq.x * Rq.x;
+                    su[1] = su[1] + Rq.y; sq[1] = sq[1] + Rq.y * Rq.y;
+                    su[2] = su[2] + Rq.z; sq[2] = sq[2] + Rq.z * Rq.z;
+                }
+            }
+            if(n > 0)
+            {
+                const float nf = (float)n;
+                const float l0 = lum709(hc[0], hc[1], hc[2]);
+                bool clipped = false;
 #pragma unroll
-                    for(int c = 0; c < 2; ++c)
-                    {
-                        const float X = ix + (float)c;
-                        const float bw = (c ? tx : 1.0f - tx) * wy;
-                        // inside on the floats; an integer only after that
-                        if(!(X >= 0.0f && X <= xmax && Y >= 0.0f && Y <= ymax)) continue;
-                        const size_t t4 = size_t((uint32_t)Y) * a.w + size_t((uint32_t)X);
-                        const float4 HA = hist_albedo[t4];
-                        if(!(HA.w > 0.0f)) continue;
-                        const float4 H = hist_radiance[t4];
-                        if(!finite3(V3(H.x, H.y, H.z))) continue;
-                        const float4 HM = hist_moments[t4];
-                        if(!(HM.w > 0.0f)) continue;
-                        const float4 HG = hist_normal_depth[t4];
-                        const float zh = HG.w / HA.w;
-                        const float zm = zh > ze ? zh : ze;
-                        if(!(fabsf(zh - ze) <= a.depth_tolerance * zm)) continue;
-                        const float nx = G.x - HG.x, ny = G.y - HG.y, nz = G.z - HG.z;
-                        const float dn = (nx * nx + ny * ny) + nz * nz;
-                        if(!(dn <= a.normal_tolerance)) continue;
-                        const float ax = A.x - HA.x, ay = A.y - HA.y, az = A.z - HA.z, aw = A.w - HA.w;
-                        const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
-                        if(!(da <= a.albedo_tolerance)) continue;
-                        sw = sw + bw;
-                        scx = scx + bw * H.x;
-                        scy = scy + bw * H.y;
-                        scz = scz + bw * H.z;
-                        s1 = s1 + bw * HM.x;
-                        s2 = s2 + bw * HM.y;
-                        sn = sn + bw * HM.w;
-                    }
+                for(int c = 0; c < 3; ++c)
+                {
+                    const float mu = su[c] / nf, e2 = sq[c] / nf;
+                    const float d = e2 - mu * mu;
+                    const float rr = a.clamp_sigma * fsqrt(d > 0.0f ? d : 0.0f);
+                    const float lo = mu - rr, hi = mu + rr;
+                    // a NaN bound compares false: the value stays
+                    if(hc[c] < lo) { hc[c] = lo; clipped = true; }
+                    else if(hc[c] > hi) { hc[c] = hi; clipped = true; }
+                }
+                if(clipped)
+                {
+                    fl = 3u;
+                    const float dl = lum709(hc[0], hc[1], hc[2]) - l0;
+                    const float g1 = h1 + dl;
+                    h2 = h2 + (g1 * g1 - h1 * h1);
+                    h1 = g1;
+                    hn = hn < a.clipped_history ? hn : a.clipped_history;
                 }
             }
         }
-    }
-    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
-    if(sw > 0.0f)
-    {
-        const float hx = scx / sw, hy = scy / sw, hz = scz / sw;
-        const float h1 = s1 / sw, h2 = s2 / sw, hn = sn / sw;
-        const float nh = hn < a.max_history ? hn : a.max_history;
-        if(finite3(V3(R.x, R.y, R.z)) && M.w > 0.0f)
-        {
-            const float nt = nh + M.w;
-            const float al = M.w / nt;
-            oc = make_float4(hx + al * (R.x - hx), hy + al * (R.y - hy), hz + al * (R.z - hz), 0.0f);
-            const float m1 = h1 + al * (M.x - h1), m2 = h2 + al * (M.y - h2);
-            om = make_float4(m1, m2, tp_var_of_mean(m1, m2, nt), nt);
-        }
-        else
-        {   // nothing usable in this frame: the history alone
-            oc = make_float4(hx, hy, hz, 0.0f);
-            om = make_float4(h1, h2, tp_var_of_mean(h1, h2, nh), nh);
-        }
+        tp_blend(hc[0], hc[1], hc[2], h1, h2, hn, a.max_history, R, M, oc, om);
     }
     out_radiance[i] = oc;
     out_moments[i] = om;
     if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
+    if(flags) flags[i] = (uint8_t)fl;
 }
 
 // ---- adaptive sampling ----
@@ -1562,6 +1691,9 @@ struct ptg_context {
     DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
     DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
     DevBuf ad_list, ad_count;              // ptg_render_adaptive: the active pixels' ids and their number
+    DevBuf tp_cams;                        // ptg_temporal_accumulate_clamped: the call's cameras (kTemporalMaxCams TemporalCam)
+    HostStage tp_stage[2];                 // their pinned staging, used alternately
+    uint32_t tp_stage_next = 0;
     uint32_t ad_passes_run = 0;            // ptg_last_adaptive_stats
     uint64_t ad_active[16] = {};
     DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
@@ -2956,6 +3088,48 @@ void ptg_temporal_params_default(ptg_temporal_params* p)
     p->albedo_tolerance = 0.25f;
 }
 
+namespace {
+
+// What ptg_temporal_accumulate and ptg_temporal_accumulate_clamped check alike.
+// *given: the history is there (all five) or not (none); *empty: the image has
+// no pixel and the call is done.
+int temporal_check(const std::string& who, uint32_t w, uint32_t h, const ptg_temporal_params& P, const ptg_camera* hist_cam,
+                   const void* const hist[4], const void* out_radiance, const void* out_moments, bool* given_out, bool* empty)
+{
+    for(float s: {P.max_history, P.depth_tolerance, P.normal_tolerance, P.albedo_tolerance})
+        if(!(s > 0.0f) || !std::isfinite(s))
+            return fail(PTG_E_INVALID, who + ": max_history and the tolerances must be positive and finite");
+    int given = hist_cam ? 1 : 0;
+    for(int k = 0; k < 4; ++k) given += hist[k] ? 1 : 0;
+    if(given != 0 && given != 5)
+        return fail(PTG_E_INVALID, who + ": hist_cam and the four hist_* images are all null or all set");
+    if(out_radiance == out_moments) return fail(PTG_E_INVALID, who + ": out_radiance and out_moments are one buffer");
+    for(int k = 0; k < 4; ++k)
+        if(hist[k] && (hist[k] == out_radiance || hist[k] == out_moments))
+            return fail(PTG_E_INVALID, who + ": an output is a hist_* image (the history is gathered from neighbours)");
+    *given_out = given != 0;
+    *empty = uint64_t(w) * h == 0;
+    if(*empty) return PTG_OK;
+    // pixel coordinates are compared as floats: exact below 2^24
+    if(uint64_t(w) * h >= (1ull << 31) || w > (1u << 24) || h > (1u << 24)) return fail(PTG_E_RANGE, "image too large");
+    return PTG_OK;
+}
+
+TemporalCam temporal_cam_of(const ptg_camera& c)
+{
+    TemporalCam t;
+    for(int k = 0; k < 3; ++k) t.ori.r[k] = f3{c.orientation.r[k].x, c.orientation.r[k].y, c.orientation.r[k].z};
+    t.pos = f3{c.position.x, c.position.y, c.position.z};
+    t.aspect = c.aspect_ratio;
+    t.ifl = c.inv_focal_length;
+    t.fd = c.focal_distance;
+    return t;
+}
+
+const float4* tp_in(const ptg_float4* p) { return reinterpret_cast<const float4*>(p); }
+
+} // namespace
+
 int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_params* params,
                             const ptg_camera* cam, const ptg_camera* hist_cam, const ptg_float4* radiance,
                             const ptg_float4* moments, const ptg_float4* albedo, const ptg_float4* normal_depth,
@@ -2967,31 +3141,11 @@ int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_
     if(!params || !cam || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
         return fail(PTG_E_INVALID, "ptg_temporal_accumulate: null argument");
     const ptg_temporal_params P = *params;
-    for(float s: {P.max_history, P.depth_tolerance, P.normal_tolerance, P.albedo_tolerance})
-        if(!(s > 0.0f) || !std::isfinite(s))
-            return fail(PTG_E_INVALID, "ptg_temporal_accumulate: max_history and the tolerances must be positive and finite");
     const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
-    int given = hist_cam ? 1 : 0;
-    for(const void* p: hist) given += p ? 1 : 0;
-    if(given != 0 && given != 5)
-        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: hist_cam and the four hist_* images are all null or all set");
-    if(static_cast<void*>(out_radiance) == static_cast<void*>(out_moments))
-        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: out_radiance and out_moments are one buffer");
-    for(const void* p: hist)
-        if(p && (p == out_radiance || p == out_moments))
-            return fail(PTG_E_INVALID, "ptg_temporal_accumulate: an output is a hist_* image (the history is gathered from neighbours)");
-    if(uint64_t(w) * h == 0) return PTG_OK;
-    // pixel coordinates are compared as floats: exact below 2^24
-    if(uint64_t(w) * h >= (1ull << 31) || w > (1u << 24) || h > (1u << 24)) return fail(PTG_E_RANGE, "image too large");
-    const auto cam_of = [](const ptg_camera& c) {
-        TemporalCam t;
-        for(int k = 0; k < 3; ++k) t.ori.r[k] = f3{c.orientation.r[k].x, c.orientation.r[k].y, c.orientation.r[k].z};
-        t.pos = f3{c.position.x, c.position.y, c.position.z};
-        t.aspect = c.aspect_ratio;
-        t.ifl = c.inv_focal_length;
-        t.fd = c.focal_distance;
-        return t;
-    };
+    bool given = false, empty = false;
+    if(int r = temporal_check("ptg_temporal_accumulate", w, h, P, hist_cam, hist, out_radiance, out_moments, &given, &empty))
+        return r;
+    if(empty) return PTG_OK;
     TemporalArgs a;
     a.w = w; a.h = h;
     a.has_history = given ? 1u : 0u;
@@ -2999,13 +3153,80 @@ int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_
     a.depth_tolerance = P.depth_tolerance;
     a.normal_tolerance = P.normal_tolerance;
     a.albedo_tolerance = P.albedo_tolerance;
-    a.cam = cam_of(*cam);
-    a.hist = cam_of(given ? *hist_cam : *cam);
-    const auto in = [](const ptg_float4* p) { return reinterpret_cast<const float4*>(p); };
-    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate, a, in(radiance), in(moments), in(albedo),
-                        in(normal_depth), in(hist_radiance), in(hist_moments), in(hist_albedo), in(hist_normal_depth),
+    a.cam = temporal_cam_of(*cam);
+    a.hist = temporal_cam_of(given ? *hist_cam : *cam);
+    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate, a, tp_in(radiance), tp_in(moments), tp_in(albedo),
+                        tp_in(normal_depth), tp_in(hist_radiance), tp_in(hist_moments), tp_in(hist_albedo),
+                        tp_in(hist_normal_depth), reinterpret_cast<float4*>(out_radiance),
+                        reinterpret_cast<float4*>(out_moments), reinterpret_cast<uchar4*>(out_bgra));
+}
+
+void ptg_temporal_clamp_params_default(ptg_temporal_clamp_params* p)
+{
+    if(!p) return;
+    ptg_temporal_params_default(&p->base);
+    // the best row of tools/denoise_study.py --temporal-clamp --sweep (profiles/denoise_study/temporal_clamp_study.json)
+    p->clamp_radius = 1;
+    p->clamp_sigma = 2.0f;
+    p->clipped_history = 32.0f;
+}
+
+int ptg_temporal_accumulate_clamped(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_clamp_params* params,
+                                    uint32_t n_cams, const ptg_camera* cams, const ptg_camera* hist_cam,
+                                    const ptg_float4* radiance, const ptg_float4* moments, const ptg_float4* albedo,
+                                    const ptg_float4* normal_depth, const ptg_float4* hist_radiance,
+                                    const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
+                                    const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments,
+                                    ptg_uchar4* out_bgra, uint8_t* out_flags)
+{
+    static const std::string who = "ptg_temporal_accumulate_clamped";
+    if(int r = bind(ctx)) return r;
+    if(!params || !cams || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
+        return fail(PTG_E_INVALID, who + ": null argument");
+    const ptg_temporal_clamp_params P = *params;
+    if(n_cams < 1 || n_cams > kTemporalMaxCams) return fail(PTG_E_INVALID, who + ": 1 .. 512 cameras");
+    if(P.clamp_radius > 2) return fail(PTG_E_INVALID, who + ": clamp_radius above 2");
+    for(float s: {P.clamp_sigma, P.clipped_history})
+        if(!(s > 0.0f) || !std::isfinite(s))
+            return fail(PTG_E_INVALID, who + ": clamp_sigma and clipped_history must be positive and finite");
+    if(P.clamp_radius > 0 && static_cast<const void*>(out_radiance) == static_cast<const void*>(radiance))
+        return fail(PTG_E_INVALID, who + ": out_radiance is radiance, which the clamp gathers from neighbours");
+    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
+    bool given = false, empty = false;
+    if(int r = temporal_check(who, w, h, P.base, hist_cam, hist, out_radiance, out_moments, &given, &empty)) return r;
+    if(empty) return PTG_OK;
+    // The cameras go through a pinned staging buffer into the context's
+    // device buffer, on the context's stream.  The device buffer is safe
+    // against reuse by stream order: the next call's copy runs behind this
+    // call's kernel.  The staging buffers alternate, and one is written again
+    // only after the copy of two calls ago that read it has completed
+    // (HostStage::reserve waits for it).
+    const size_t bytes = size_t(n_cams) * sizeof(TemporalCam);
+    PTG_HIP(ctx->grow(ctx->tp_cams, size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
+    HostStage& hs = ctx->tp_stage[ctx->tp_stage_next];
+    ctx->tp_stage_next ^= 1u;
+    PTG_HIP(hs.reserve(size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
+    TemporalCam* staged = static_cast<TemporalCam*>(hs.p);
+    for(uint32_t k = 0; k < n_cams; ++k) staged[k] = temporal_cam_of(cams[k]);
+    PTG_HIP(hipMemcpyAsync(ctx->tp_cams.p, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PTG_HIP(hipEventRecord(hs.done, ctx->stream));
+    TemporalClampArgs a;
+    a.w = w; a.h = h;
+    a.has_history = given ? 1u : 0u;
+    a.n_cams = n_cams;
+    a.clamp_radius = P.clamp_radius;
+    a.max_history = P.base.max_history;
+    a.depth_tolerance = P.base.depth_tolerance;
+    a.normal_tolerance = P.base.normal_tolerance;
+    a.albedo_tolerance = P.base.albedo_tolerance;
+    a.clamp_sigma = P.clamp_sigma;
+    a.clipped_history = P.clipped_history;
+    a.hist = temporal_cam_of(given ? *hist_cam : cams[0]);
+    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate_clamped, a, ctx->tp_cams.as<const TemporalCam>(),
+                        tp_in(radiance), tp_in(moments), tp_in(albedo), tp_in(normal_depth), tp_in(hist_radiance),
+                        tp_in(hist_moments), tp_in(hist_albedo), tp_in(hist_normal_depth),
                         reinterpret_cast<float4*>(out_radiance), reinterpret_cast<float4*>(out_moments),
-                        reinterpret_cast<uchar4*>(out_bgra));
+                        reinterpret_cast<uchar4*>(out_bgra), out_flags);
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

@@ -11,7 +11,9 @@ kernels give; it is the documented CPU route and the tests' checker.
 Further down: the sample moments and the variance-guided filter
 (``moments_reference``, ``atrous_guided_reference``), and the temporal
 accumulation (``TemporalParams``, ``temporal_reference``: the restatement of
-``ptg_temporal_accumulate``).
+``ptg_temporal_accumulate``), and its form with several
+cameras and a history clamp (``TemporalClampParams``,
+``temporal_clamped_reference``: ``ptg_temporal_accumulate_clamped``, 4.17).
 """
 from __future__ import annotations
 
@@ -287,6 +289,119 @@ def _var_of_mean(m1, m2, n):
     return np.where(n >= 2, var / (n - f32(1)), f32(0)).astype(f32)
 
 
+def _temporal_images(radiance, moments, albedo, normal_depth, hist):
+    """The float32 images of a temporal call, checked: (R, M, A, G), the
+    history's (H, HM, HA, HG) or None on a first frame."""
+    f32 = np.float32
+    cur = tuple(np.ascontiguousarray(a, dtype=f32) for a in (radiance, moments, albedo, normal_depth))
+    h, w = cur[0].shape[:2]
+    assert all(a.shape == (h, w, 4) for a in cur)
+    given = sum(a is not None for a in hist)
+    if given not in (0, 5):
+        raise ValueError("hist_cam and the four hist_* images are all None or all given")
+    if not given:
+        return cur, None
+    old = tuple(np.ascontiguousarray(a, dtype=f32) for a in hist[1:])
+    assert all(a.shape == (h, w, 4) for a in old)
+    return cur, old
+
+
+class _TemporalSums:
+    """The seven running sums of the reprojection: sw, sc.xyz, s1, s2, sn."""
+
+    def __init__(self, h, w):
+        f32 = np.float32
+        self.sw = np.zeros((h, w), f32)
+        self.sc = np.zeros((h, w, 3), f32)
+        self.s1, self.s2, self.sn = np.zeros((h, w), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
+
+
+def _temporal_gather(S, cam, hist_cam, A, G, old, P):
+    """Steps 1-4 of DESIGN.md 4.13 for one camera: every valid tap adds into
+    the sums S.  A pixel that fails a test through this camera adds nothing."""
+    f32 = np.float32
+    H, HM, HA, HG = old
+    h, w = A.shape[:2]
+    ori, pos, aspect, ifl, fd = _camera_parts(cam)
+    hori, hpos, haspect, hifl, _ = _camera_parts(hist_cam)
+    tz, tn, ta = f32(P.depth_tolerance), f32(P.normal_tolerance), f32(P.albedo_tolerance)
+    wf, hf = f32(w), f32(h)
+    # 1-2: the pixel's first-hit point
+    cov = A[..., 3]
+    ok = cov > 0
+    z = G[..., 3] / cov
+    xs = np.arange(w, dtype=f32)[None, :].repeat(h, 0)
+    ys = np.arange(h, dtype=f32)[:, None].repeat(w, 1)
+    uvx = ((xs + f32(0.5)) / wf * f32(2) - f32(1)) * aspect
+    uvy = -((ys + f32(0.5)) / hf * f32(2) - f32(1))
+    dx, dy, dz = uvx * ifl * fd, uvy * ifl * fd, np.full((h, w), f32(-1) * fd, f32)
+    ln = np.sqrt(_dot3(dx, dy, dz, dx, dy, dz))
+    dx, dy, dz = dx / ln, dy / ln, dz / ln
+    # mul_m3v3(ori, d): component c is the dot of (r0.c, r1.c, r2.c) with d
+    dirv = [_dot3(ori[0, c], ori[1, c], ori[2, c], dx, dy, dz) for c in range(3)]
+    Pw = [pos[c] + dirv[c] * z for c in range(3)]
+    # 3: into the history camera
+    q = [Pw[c] - hpos[c] for c in range(3)]
+    l = [_dot3(hori[r, 0], hori[r, 1], hori[r, 2], q[0], q[1], q[2]) for r in range(3)]   # mul_v3m3(q, ori)
+    ok &= l[2] < 0
+    t = -l[2]
+    sx = (l[0] / t) / hifl / haspect
+    sy = -((l[1] / t) / hifl)
+    fx = (sx + f32(1)) * f32(0.5) * wf - f32(0.5)
+    fy = (sy + f32(1)) * f32(0.5) * hf - f32(0.5)
+    ze = np.sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2])
+    ok &= np.isfinite(fx) & np.isfinite(fy)
+    # 4: the bilinear taps, b (rows) outer and a (columns) inner
+    ix, iy = np.floor(fx), np.floor(fy)
+    tx, ty = fx - ix, fy - iy
+    for b in (0, 1):
+        Y = iy + f32(b)
+        wy = ty if b else f32(1) - ty
+        for a in (0, 1):
+            X = ix + f32(a)
+            bw = (tx if a else f32(1) - tx) * wy
+            v = ok & (X >= 0) & (X <= f32(w - 1)) & (Y >= 0) & (Y <= f32(h - 1))
+            xi = np.where(v, X, f32(0)).astype(np.int64)
+            yi = np.where(v, Y, f32(0)).astype(np.int64)
+            Hq, HMq, HAq, HGq = H[yi, xi], HM[yi, xi], HA[yi, xi], HG[yi, xi]
+            v &= HAq[..., 3] > 0
+            v &= np.isfinite(Hq[..., :3]).all(-1)
+            v &= HMq[..., 3] > 0
+            zh = HGq[..., 3] / HAq[..., 3]
+            v &= np.abs(zh - ze) <= tz * np.where(zh > ze, zh, ze)
+            v &= _sq3(G[..., :3] - HGq[..., :3]) <= tn
+            d = A - HAq
+            v &= (_sq3(d) + d[..., 3] * d[..., 3]) <= ta
+            S.sw = np.where(v, S.sw + bw, S.sw)
+            S.sc = np.where(v[..., None], S.sc + bw[..., None] * Hq[..., :3], S.sc)
+            S.s1 = np.where(v, S.s1 + bw * HMq[..., 0], S.s1)
+            S.s2 = np.where(v, S.s2 + bw * HMq[..., 1], S.s2)
+            S.sn = np.where(v, S.sn + bw * HMq[..., 3], S.sn)
+
+
+def _temporal_blend(some, Hc, h1, h2, hn, max_history, R, M):
+    """Steps 5-7: (out_radiance, out_moments) of the history (Hc, h1, h2, hn)
+    where `some`, blended with this frame's R and M."""
+    f32 = np.float32
+    mh = f32(max_history)
+    out_c = R.copy()
+    out_c[..., 3] = 0
+    nh = np.where(hn < mh, hn, mh)
+    nc = M[..., 3]
+    both = some & np.isfinite(R[..., :3]).all(-1) & (nc > 0)
+    nt = nh + nc
+    al = nc / nt
+    c6 = Hc + al[..., None] * (R[..., :3] - Hc)
+    m1 = h1 + al * (M[..., 0] - h1)
+    m2 = h2 + al * (M[..., 1] - h2)
+    mom6 = np.stack([m1, m2, _var_of_mean(m1, m2, nt), nt], -1)
+    mom7 = np.stack([h1, h2, _var_of_mean(h1, h2, nh), nh], -1)
+    out_c[..., :3] = np.where(both[..., None], c6, np.where(some[..., None], Hc, R[..., :3]))
+    out_m = np.where(both[..., None], mom6, np.where(some[..., None], mom7, M))
+    assert out_c.dtype == f32 and out_m.dtype == f32
+    return out_c, np.ascontiguousarray(out_m)
+
+
 def temporal_reference(cam, hist_cam, radiance, moments, albedo, normal_depth, hist_radiance=None, hist_moments=None,
                        hist_albedo=None, hist_normal_depth=None, params: TemporalParams = None, found=None):
     """ptg_temporal_accumulate on the CPU: [h, w, 4] float32 arrays in,
@@ -296,99 +411,136 @@ def temporal_reference(cam, hist_cam, radiance, moments, albedo, normal_depth, h
     passed as `found` is set where a pixel found history."""
     P = params if params is not None else TemporalParams.default()
     P.validate()
-    f32 = np.float32
-    R, M, A, G = (np.ascontiguousarray(a, dtype=f32) for a in (radiance, moments, albedo, normal_depth))
+    (R, M, A, G), old = _temporal_images(radiance, moments, albedo, normal_depth,
+                                         (hist_cam, hist_radiance, hist_moments, hist_albedo, hist_normal_depth))
     h, w = R.shape[:2]
-    assert R.shape == M.shape == A.shape == G.shape == (h, w, 4)
-    hist = (hist_cam, hist_radiance, hist_moments, hist_albedo, hist_normal_depth)
-    given = sum(a is not None for a in hist)
-    if given not in (0, 5):
-        raise ValueError("hist_cam and the four hist_* images are all None or all given")
-    out_c = R.copy()
-    out_c[..., 3] = 0
-    out_m = M.copy()
     if found is not None:
         found[...] = False
-    if not given or w * h == 0:
-        return out_c, out_m
-    H, HM, HA, HG = (np.ascontiguousarray(a, dtype=f32) for a in hist[1:])
-    assert H.shape == HM.shape == HA.shape == HG.shape == (h, w, 4)
-    ori, pos, aspect, ifl, fd = _camera_parts(cam)
-    hori, hpos, haspect, hifl, _ = _camera_parts(hist_cam)
-    mh, tz, tn, ta = f32(P.max_history), f32(P.depth_tolerance), f32(P.normal_tolerance), f32(P.albedo_tolerance)
-    wf, hf = f32(w), f32(h)
+    if old is None or w * h == 0:
+        out_c = R.copy()
+        out_c[..., 3] = 0
+        return out_c, M.copy()
     with np.errstate(all="ignore"):
-        # 1-2: the pixel's first-hit point
-        cov = A[..., 3]
-        ok = cov > 0
-        z = G[..., 3] / cov
-        xs = np.arange(w, dtype=f32)[None, :].repeat(h, 0)
-        ys = np.arange(h, dtype=f32)[:, None].repeat(w, 1)
-        uvx = ((xs + f32(0.5)) / wf * f32(2) - f32(1)) * aspect
-        uvy = -((ys + f32(0.5)) / hf * f32(2) - f32(1))
-        dx, dy, dz = uvx * ifl * fd, uvy * ifl * fd, np.full((h, w), f32(-1) * fd, f32)
-        ln = np.sqrt(_dot3(dx, dy, dz, dx, dy, dz))
-        dx, dy, dz = dx / ln, dy / ln, dz / ln
-        # mul_m3v3(ori, d): component c is the dot of (r0.c, r1.c, r2.c) with d
-        dirv = [_dot3(ori[0, c], ori[1, c], ori[2, c], dx, dy, dz) for c in range(3)]
-        Pw = [pos[c] + dirv[c] * z for c in range(3)]
-        # 3: into the history camera
-        q = [Pw[c] - hpos[c] for c in range(3)]
-        l = [_dot3(hori[r, 0], hori[r, 1], hori[r, 2], q[0], q[1], q[2]) for r in range(3)]   # mul_v3m3(q, ori)
-        ok &= l[2] < 0
-        t = -l[2]
-        sx = (l[0] / t) / hifl / haspect
-        sy = -((l[1] / t) / hifl)
-        fx = (sx + f32(1)) * f32(0.5) * wf - f32(0.5)
-        fy = (sy + f32(1)) * f32(0.5) * hf - f32(0.5)
-        ze = np.sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2])
-        ok &= np.isfinite(fx) & np.isfinite(fy)
-        # 4: the bilinear taps, b (rows) outer and a (columns) inner
-        ix, iy = np.floor(fx), np.floor(fy)
-        tx, ty = fx - ix, fy - iy
-        sw = np.zeros((h, w), f32)
-        sc = np.zeros((h, w, 3), f32)
-        s1, s2, sn = np.zeros((h, w), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
-        for b in (0, 1):
-            Y = iy + f32(b)
-            wy = ty if b else f32(1) - ty
-            for a in (0, 1):
-                X = ix + f32(a)
-                bw = (tx if a else f32(1) - tx) * wy
-                v = ok & (X >= 0) & (X <= f32(w - 1)) & (Y >= 0) & (Y <= f32(h - 1))
-                xi = np.where(v, X, f32(0)).astype(np.int64)
-                yi = np.where(v, Y, f32(0)).astype(np.int64)
-                Hq, HMq, HAq, HGq = H[yi, xi], HM[yi, xi], HA[yi, xi], HG[yi, xi]
-                v &= HAq[..., 3] > 0
-                v &= np.isfinite(Hq[..., :3]).all(-1)
-                v &= HMq[..., 3] > 0
-                zh = HGq[..., 3] / HAq[..., 3]
-                v &= np.abs(zh - ze) <= tz * np.where(zh > ze, zh, ze)
-                v &= _sq3(G[..., :3] - HGq[..., :3]) <= tn
-                d = A - HAq
-                v &= (_sq3(d) + d[..., 3] * d[..., 3]) <= ta
-                sw = np.where(v, sw + bw, sw)
-                sc = np.where(v[..., None], sc + bw[..., None] * Hq[..., :3], sc)
-                s1 = np.where(v, s1 + bw * HMq[..., 0], s1)
-                s2 = np.where(v, s2 + bw * HMq[..., 1], s2)
-                sn = np.where(v, sn + bw * HMq[..., 3], sn)
-        some = sw > 0
-        Hc = sc / sw[..., None]
-        h1, h2, hn = s1 / sw, s2 / sw, sn / sw
-        # 5-7: the blend
-        nh = np.where(hn < mh, hn, mh)
-        nc = M[..., 3]
-        both = some & np.isfinite(R[..., :3]).all(-1) & (nc > 0)
-        nt = nh + nc
-        al = nc / nt
-        c6 = Hc + al[..., None] * (R[..., :3] - Hc)
-        m1 = h1 + al * (M[..., 0] - h1)
-        m2 = h2 + al * (M[..., 1] - h2)
-        mom6 = np.stack([m1, m2, _var_of_mean(m1, m2, nt), nt], -1)
-        mom7 = np.stack([h1, h2, _var_of_mean(h1, h2, nh), nh], -1)
-        out_c[..., :3] = np.where(both[..., None], c6, np.where(some[..., None], Hc, R[..., :3]))
-        out_m = np.where(both[..., None], mom6, np.where(some[..., None], mom7, M))
+        S = _TemporalSums(h, w)
+        _temporal_gather(S, cam, hist_cam, A, G, old, P)
+        some = S.sw > 0
+        out = _temporal_blend(some, S.sc / S.sw[..., None], S.s1 / S.sw, S.s2 / S.sw, S.sn / S.sw, P.max_history, R, M)
     if found is not None:
         found[...] = some
-    assert out_c.dtype == f32 and out_m.dtype == f32
-    return out_c, np.ascontiguousarray(out_m)
+    return out
+
+
+# ---- temporal accumulation over several cameras, with a history clamp ----------
+
+
+class TemporalClampParams(_Params, C.Structure):
+    """ptg_temporal_clamp_params.  ``TemporalClampParams.default()`` asks the
+    library; ``base`` is a TemporalParams."""
+    _fields_ = [("base", TemporalParams), ("clamp_radius", C.c_uint32), ("clamp_sigma", C.c_float),
+                ("clipped_history", C.c_float)]
+    _default_fn = "ptg_temporal_clamp_params_default"
+    _positive = ("clamp_sigma", "clipped_history")
+    MAX_RADIUS = 2
+
+    def as_dict(self):
+        return dict(_Params.as_dict(self), base=self.base.as_dict())
+
+    def validate(self):
+        self.base.validate()
+        if self.clamp_radius > self.MAX_RADIUS:
+            raise ValueError("clamp_radius > %d" % self.MAX_RADIUS)
+        _Params.validate(self)
+
+
+MAX_CAMERAS = 512                                # ptg_temporal_accumulate_clamped's n_cams
+
+
+def clamp_box(radiance, radius, sigma):
+    """The clamp's colour box of every pixel: (n [h, w] int, lo, hi [h, w, 3]
+    float32) from the (2 radius + 1)^2 window of `radiance`, dy outer and dx
+    inner, taps outside the image or with a non-finite channel left out;
+    lo / hi = mean -+ sigma * standard deviation.  Where n is 0 the bounds
+    mean nothing."""
+    f32 = np.float32
+    R = np.ascontiguousarray(radiance, dtype=f32)[..., :3]
+    h, w = R.shape[:2]
+    fin = np.isfinite(R).all(-1)
+    n = np.zeros((h, w), np.int64)
+    su = np.zeros((h, w, 3), f32)
+    sq = np.zeros((h, w, 3), f32)
+    with np.errstate(all="ignore"):
+        for dy in range(-radius, radius + 1):
+            y0, y1 = max(0, -dy), min(h, h - dy)
+            if y0 >= y1:
+                continue
+            for dx in range(-radius, radius + 1):
+                x0, x1 = max(0, -dx), min(w, w - dx)
+                if x0 >= x1:
+                    continue
+                ps = (slice(y0, y1), slice(x0, x1))
+                qs = (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
+                v = fin[qs]
+                Rq = R[qs]
+                n[ps] += v
+                su[ps] = np.where(v[..., None], su[ps] + Rq, su[ps])
+                sq[ps] = np.where(v[..., None], sq[ps] + Rq * Rq, sq[ps])
+        nf = n.astype(f32)[..., None]
+        mu = su / nf
+        e2 = sq / nf
+        d = e2 - mu * mu
+        rr = f32(sigma) * np.sqrt(np.where(d > 0, d, f32(0)))
+        return n, mu - rr, mu + rr
+
+
+def temporal_clamped_reference(cams, hist_cam, radiance, moments, albedo, normal_depth, hist_radiance=None,
+                               hist_moments=None, hist_albedo=None, hist_normal_depth=None,
+                               params: TemporalClampParams = None, found=None, clipped=None):
+    """ptg_temporal_accumulate_clamped on the CPU:
+    temporal_reference with the reprojection run once per camera of `cams` (a
+    sequence of 1 .. 512 CAMERA_DTYPE records or ctypes ptg_camera structures)
+    into the same sums, and, with params.clamp_radius > 0, the history clamped
+    to this frame's local colour box.  Bool [h, w] arrays passed as `found` /
+    `clipped` are set where a pixel found history / had it clipped."""
+    P = params if params is not None else TemporalClampParams.default()
+    P.validate()
+    cams = list(cams) if not isinstance(cams, np.ndarray) else [c for c in cams.reshape(-1)]
+    if not 1 <= len(cams) <= MAX_CAMERAS:
+        raise ValueError("1 .. %d cameras, got %d" % (MAX_CAMERAS, len(cams)))
+    (R, M, A, G), old = _temporal_images(radiance, moments, albedo, normal_depth,
+                                         (hist_cam, hist_radiance, hist_moments, hist_albedo, hist_normal_depth))
+    h, w = R.shape[:2]
+    for flag in (found, clipped):
+        if flag is not None:
+            flag[...] = False
+    if old is None or w * h == 0:
+        out_c = R.copy()
+        out_c[..., 3] = 0
+        return out_c, M.copy()
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        S = _TemporalSums(h, w)
+        for cam in cams:
+            _temporal_gather(S, cam, hist_cam, A, G, old, P.base)
+        some = S.sw > 0
+        Hc, h1, h2, hn = S.sc / S.sw[..., None], S.s1 / S.sw, S.s2 / S.sw, S.sn / S.sw
+        clip = np.zeros((h, w), bool)
+        if P.clamp_radius > 0:
+            n, lo, hi = clamp_box(R, int(P.clamp_radius), P.clamp_sigma)
+            below = Hc < lo
+            above = ~below & (Hc > hi)
+            Hk = np.where(below, lo, np.where(above, hi, Hc))
+            clip = some & (n > 0) & (below | above).any(-1)
+            dl = _lum(Hk) - _lum(Hc)
+            g1 = h1 + dl
+            g2 = h2 + (g1 * g1 - h1 * h1)
+            ch = f32(P.clipped_history)
+            Hc = np.where(clip[..., None], Hk, Hc)
+            h2 = np.where(clip, g2, h2)
+            h1 = np.where(clip, g1, h1)
+            hn = np.where(clip, np.where(hn < ch, hn, ch), hn)
+        out = _temporal_blend(some, Hc, h1, h2, hn, P.base.max_history, R, M)
+    if found is not None:
+        found[...] = some
+    if clipped is not None:
+        clipped[...] = clip
+    return out

@@ -141,6 +141,8 @@ def lib():
         "ptg_denoise_guided": (I, [P, U32, U32, P, P, P, P, P, P, P]),
         "ptg_temporal_params_default": (None, [P]),
         "ptg_temporal_accumulate": (I, [P, U32, U32, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+        "ptg_temporal_clamp_params_default": (None, [P]),
+        "ptg_temporal_accumulate_clamped": (I, [P, U32, U32, P, U32, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
         "ptg_adaptive_params_default": (None, [P]),
         "ptg_render_adaptive": (I, [P, P, U32, U32, U32, U32, P, P, P, P, P]),
         "ptg_last_adaptive_stats": (I, [P, C.POINTER(U32), P]),

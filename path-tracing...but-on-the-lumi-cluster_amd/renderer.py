@@ -289,6 +289,49 @@ class GpuRenderer:
                                                 _ptr(out_moments), _ptr(bgra)), "ptg_temporal_accumulate")
         return out_radiance, out_moments, bgra
 
+    def temporal_accumulate_clamped(self, cams, radiance, moments, albedo, normal_depth, history=None, params=None,
+                                    want_bgra=False, out_radiance=None, out_moments=None, want_flags=False):
+        """ptg_temporal_accumulate_clamped: temporal_accumulate through the
+        list `cams` of this frame's cameras (1 .. 512 native.Camera or
+        CAMERA_DTYPE records, e.g. a motion-blurred frame's subframe cameras),
+        the history clamped to the frame's local colour box as `params` (a
+        denoise.TemporalClampParams) says.  Returns (accumulated radiance,
+        accumulated moments, bgra or None), and with `want_flags` a fourth
+        value: the uint8 [h, w] device tensor of the pixels' flags, written
+        on the context's stream like the images (``split_flags`` gives the
+        found and the clipped mask).  `out_moments` may be `moments`;
+        `out_radiance` may be `radiance` only with clamp_radius 0.
+        Asynchronous."""
+        import torch
+        from .denoise import TemporalClampParams
+        p = params if params is not None else TemporalClampParams.default()
+        images = (radiance, moments, albedo, normal_depth) + (tuple(history[1:]) if history is not None else ())
+        h, w = radiance.shape[:2]
+        for t in images:
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        cams = [cams[k] for k in range(len(cams))] if isinstance(cams, np.ndarray) else list(cams)
+        c = (N.Camera * max(len(cams), 1))(*(N.Camera.of(cam) for cam in cams))
+        hc = N.Camera.of(history[0]) if history is not None else None
+        if out_radiance is None:
+            out_radiance = torch.empty_like(radiance)
+        if out_moments is None:
+            out_moments = torch.empty_like(moments)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
+        flags = torch.empty((h, w), dtype=torch.uint8, device=radiance.device) if want_flags else None
+        hist = images[4:] if history is not None else (None,) * 4
+        N.check(N.lib().ptg_temporal_accumulate_clamped(self._ctx, w, h, C.byref(p), len(cams), c,
+                                                        C.byref(hc) if hc is not None else None, *map(_ptr, images[:4]),
+                                                        *map(_ptr, hist), _ptr(out_radiance), _ptr(out_moments), _ptr(bgra),
+                                                        _ptr(flags)), "ptg_temporal_accumulate_clamped")
+        return (out_radiance, out_moments, bgra, flags) if want_flags else (out_radiance, out_moments, bgra)
+
+    @staticmethod
+    def split_flags(flags):
+        """(found, clipped) bool masks of temporal_accumulate_clamped's flags
+        (a tensor, after a synchronize, or its numpy copy): bit 0 the pixel
+        found history, bit 1 its history was clipped."""
+        return (flags & 1) != 0, (flags & 2) != 0
+
     def tonemap_device(self, colors, out_bgra):
         """tonemap_pixel over a device float32 [..., 4] tensor into a device
         uint8 [..., 4] tensor (ptg_tonemap_device; asynchronous)."""
@@ -436,15 +479,34 @@ class TemporalDenoiser:
     with render_adaptive (cfg.samples_per_pixel is then the budget) instead
     of render_moments; the accumulation and the filter take its moments,
     whose sample count varies per pixel, as they are.  None (the default)
-    renders with render_moments."""
+    renders with render_moments.
+
+    ``clamp_params`` / ``blur_cameras``: with both at their defaults (None, 1)
+    the step accumulates with temporal_accumulate, as above.  A
+    ``denoise.TemporalClampParams`` as ``clamp_params`` makes it call
+    temporal_accumulate_clamped with them instead (its ``base`` is then the
+    accumulation's parameters, and ``temporal_params`` must be None); the
+    radiance is then not accumulated in place, since the clamp reads this
+    frame's neighbours.  ``blur_cameras = K > 1`` passes min(K, S) of the
+    frame's S subframe cameras, evenly spaced (subframe
+    ((2 k + 1) S) // (2 min(K, S)) for k = 0 ..), so that the history is
+    gathered along the frame's motion blur; without ``clamp_params`` the clamp
+    is then off (clamp_radius 0).  The history's camera stays the previous
+    frame's middle subframe camera."""
 
     def __init__(self, renderer: GpuRenderer, cfg: N.RenderConfig, temporal_params=None, guided_params=None,
-                 seed_stride=1, adaptive_params=None):
+                 seed_stride=1, adaptive_params=None, clamp_params=None, blur_cameras=1):
+        if clamp_params is not None and temporal_params is not None:
+            raise ValueError("clamp_params.base holds the accumulation's parameters: pass no temporal_params beside it")
+        if int(blur_cameras) < 1:
+            raise ValueError("blur_cameras must be at least 1")
         self.renderer = renderer
         self.cfg = cfg
         self.temporal_params = temporal_params
         self.guided_params = guided_params
         self.adaptive_params = adaptive_params
+        self.clamp_params = clamp_params
+        self.blur_cameras = int(blur_cameras)
         self.seed_stride = int(seed_stride)
         self.reset()
 
@@ -459,6 +521,12 @@ class TemporalDenoiser:
                               (c.student_id + self.frames * self.seed_stride) & 0xFFFFFFFF,
                               c.samples_per_motion_blur_step)
 
+    def blur_subframes(self, count):
+        """The subframes whose cameras a step passes, of a frame with `count`:
+        min(blur_cameras, count) evenly spaced; one is the middle subframe."""
+        k = min(self.blur_cameras, count)
+        return [((2 * j + 1) * count) // (2 * k) for j in range(k)]
+
     def step(self, scene: N.Scene):
         r = self.renderer
         cfg = self.frame_config()
@@ -470,9 +538,22 @@ class TemporalDenoiser:
         else:
             _, acc, moments = r.render_moments(cfg, want_accum=True)
         albedo, normal_depth = r.render_features(cfg)
-        # in place: this frame's radiance and moments become the accumulated ones
-        acc, moments, _ = r.temporal_accumulate(cam, acc, moments, albedo, normal_depth, self.history, self.temporal_params,
-                                                out_radiance=acc, out_moments=moments)
+        if self.clamp_params is None and self.blur_cameras == 1:
+            # in place: this frame's radiance and moments become the accumulated ones
+            acc, moments, _ = r.temporal_accumulate(cam, acc, moments, albedo, normal_depth, self.history,
+                                                    self.temporal_params, out_radiance=acc, out_moments=moments)
+        else:
+            from .denoise import TemporalClampParams
+            p = self.clamp_params
+            if p is None:
+                p = TemporalClampParams.default(clamp_radius=0)
+                if self.temporal_params is not None:
+                    p.base = self.temporal_params
+            cams = [subframes[k]["cam"] for k in self.blur_subframes(len(subframes))]
+            # the moments in place; the radiance never with clamp_params: a clamp gathers it from neighbours
+            acc, moments, _ = r.temporal_accumulate_clamped(cams, acc, moments, albedo, normal_depth, self.history, p,
+                                                            out_radiance=acc if self.clamp_params is None else None,
+                                                            out_moments=moments)
         out, bgra = r.denoise_guided(acc, albedo, normal_depth, moments, self.guided_params, want_bgra=True)
         self.history = (cam, acc, moments, albedo, normal_depth)
         self.frames += 1

@@ -45,7 +45,20 @@ gain over uniform sampling of the four (frame, budget) cells; the library's
 defaults (ptg_adaptive_params_default) are the best row of the recorded sweep.
 Writes <out>/adaptive_study.json.
 
-Usage: python tools/denoise_study.py [--guided | --temporal | --adaptive] [--sweep] [--out profiles/<name>]
+--temporal-clamp studies the two remedies DESIGN.md 4.13 names for a frame
+whose camera moves (ptg_temporal_accumulate_clamped through TemporalDenoiser's
+clamp_params and blur_cameras): the set-up of --temporal with seed_stride 1,
+and per row four arms - today's accumulation, the frame's subframe cameras
+alone (blur_cameras 8), the history clamp alone, both - each as accumulated /
+accumulated + guided PSNR with the found and the clipped share of the last
+frame; and the kernel's time at 1, 8 and 128 cameras (HIP events, mean of 20
+calls).  With --sweep it first ranks clamp_radius x clamp_sigma x
+clipped_history by the ranking rule of --temporal on the arm with both
+remedies and uses the best row; the library's defaults
+(ptg_temporal_clamp_params_default) are the best row of the recorded sweep.
+Writes <out>/temporal_clamp_study.json.
+
+Usage: python tools/denoise_study.py [--guided | --temporal | --temporal-clamp | --adaptive] [--sweep] [--out profiles/<name>]
 Writes <out>/denoise_study.json.
 """
 import argparse
@@ -64,7 +77,7 @@ import ptlumi_loader  # noqa: E402
 
 P = ptlumi_loader.load()
 N, V = P.native, P.validator
-from ptlumi.denoise import DenoiseGuidedParams, DenoiseParams, TemporalParams  # noqa: E402
+from ptlumi.denoise import DenoiseGuidedParams, DenoiseParams, TemporalClampParams, TemporalParams  # noqa: E402
 
 ASSETS = os.path.join(ROOT, "assets")
 W, H = 1280, 720
@@ -372,6 +385,151 @@ def temporal_study(args):
     print("wrote", os.path.join(args.out, "temporal_study.json"))
 
 
+CLAMP_GRID = {"clamp_radius": (1, 2), "clamp_sigma": (0.5, 1.0, 2.0, 4.0), "clipped_history": (8.0, 32.0, 128.0)}
+CLAMP_BLUR_CAMERAS = 8
+CLAMP_TIMED_CAMERAS = (1, 8, 128)
+CLAMP_ARMS = ("today", "cameras", "clamp", "both")
+
+
+def temporal_clamp_study(args):
+    r = P.GpuRenderer(0)
+    result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP, "spps": TEMPORAL_SPPS,
+                         "preceding": TEMPORAL_PRECEDING, "seed_stride": 1, "blur_cameras": CLAMP_BLUR_CAMERAS,
+                         "arms": CLAMP_ARMS, "sequences": {str(f): sequence(f, 8) for f in FRAMES}},
+              "device": torch.cuda.get_device_name(0)}
+    cfg = N.RenderConfig.make(W, H, REF_SPP)
+    scene = N.Scene(ASSETS, cfg)
+    ref_half = {}
+    for f in FRAMES:
+        scene.setup_frame(f)
+        r.upload(scene)
+        bgra, _ = r.render(cfg)
+        r.synchronize()
+        ref_half[f] = V.downscale_half(V.bgra_to_rgb(bgra.cpu().numpy()))
+    scene.close()
+
+    def tonemapped(radiance):
+        return r.tonemap_device(radiance, torch.empty(radiance.shape, dtype=torch.uint8, device=radiance.device))
+
+    def frames_of(scene, cfg, frames):
+        """Per frame of the sequence what TemporalDenoiser.step renders: (subframe cameras, radiance, moments, albedo,
+        normal_depth)."""
+        td = P.TemporalDenoiser(r, cfg, seed_stride=1)
+        out = []
+        for f in frames:
+            scene.setup_frame(f)
+            r.upload(scene)
+            cams = [N.Camera.of(s["cam"]) for s in scene.view()["subframes"]]
+            c = td.frame_config()
+            _, acc, mom = r.render_moments(c, want_accum=True)
+            out.append((cams, acc, mom) + r.render_features(c))
+            td.frames += 1
+        return out
+
+    def accumulate(steps, cp, blur_cameras):
+        """The sequence as TemporalDenoiser.step chains it with clamp_params `cp` and `blur_cameras` (not in place):
+        (history, found share, clipped share of the last step)."""
+        td = P.TemporalDenoiser(r, None, clamp_params=cp, blur_cameras=blur_cameras)
+        hist, flags = None, None
+        for cams, acc, mom, alb, nd in steps:
+            use = [cams[k] for k in td.blur_subframes(len(cams))]
+            rad, m, _, flags = r.temporal_accumulate_clamped(use, acc, mom, alb, nd, hist, cp, want_flags=True)
+            hist = (cams[len(cams) // 2], rad, m, alb, nd)
+        r.synchronize()
+        found, clipped = r.split_flags(flags)
+        return hist, float(found.float().mean()), float(clipped.float().mean())
+
+    def arms_of(cp):
+        off = TemporalClampParams.default(clamp_radius=0)
+        off.base = cp.base
+        return {"today": (off, 1), "cameras": (off, CLAMP_BLUR_CAMERAS), "clamp": (cp, 1), "both": (cp, CLAMP_BLUR_CAMERAS)}
+
+    cparams, gparams = TemporalClampParams.default(), DenoiseGuidedParams.default()
+    result["library_params"] = cparams.as_dict()
+    if args.sweep:
+        held = {}
+        for spp in TEMPORAL_SWEEP_SPPS:
+            cfg = N.RenderConfig.make(W, H, spp)
+            scene = N.Scene(ASSETS, cfg)
+            for f in FRAMES:
+                held[spp, f] = frames_of(scene, cfg, sequence(f, TEMPORAL_SWEEP_PRECEDING))
+            scene.close()
+        rows = []
+        keys = list(CLAMP_GRID)
+
+        def cells(cp, blur_cameras):
+            ps = {}
+            for (spp, f), steps in held.items():
+                h, _, _ = accumulate(steps, cp, blur_cameras)
+                _, bgra = r.denoise_guided(h[1], h[3], h[4], h[2], gparams)
+                ps["%d@%d" % (f, spp)] = psnr_half(ref_half[f], bgra)
+            return ps
+
+        off = arms_of(cparams)["today"][0]
+        baseline = {"today": cells(off, 1), "cameras": cells(off, CLAMP_BLUR_CAMERAS)}
+        for combo in itertools.product(*(CLAMP_GRID[k] for k in keys)):
+            cp = TemporalClampParams.default(**dict(zip(keys, combo)))
+            both, alone = cells(cp, CLAMP_BLUR_CAMERAS), cells(cp, 1)
+            rows.append(dict(zip(keys, combo), psnr=both, mean=float(np.mean(list(both.values()))), clamp_only=alone,
+                             clamp_only_mean=float(np.mean(list(alone.values())))))
+            print("sweep:", json.dumps(rows[-1]), flush=True)
+        rows.sort(key=lambda x: -x["mean"])
+        best = rows[0]
+        cparams = TemporalClampParams.default(**{k: best[k] for k in keys})
+        result["sweep"] = {"spps": TEMPORAL_SWEEP_SPPS, "preceding": TEMPORAL_SWEEP_PRECEDING, "seed_stride": 1,
+                           "grid": CLAMP_GRID, "ranked_on": "both", "best": best, "rows": rows,
+                           "without_clamp": {k: dict(psnr=v, mean=float(np.mean(list(v.values())))) for k, v in baseline.items()}}
+        print("sweep: best", best, flush=True)
+        del held
+    result["params"] = cparams.as_dict()
+    result["guided_params"] = gparams.as_dict()
+
+    table, timing = [], []
+    for spp in TEMPORAL_SPPS:
+        cfg = N.RenderConfig.make(W, H, spp)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene)
+            raw, racc, rmom = r.render_moments(cfg, want_accum=True)
+            ralb, rnd = r.render_features(cfg)
+            _, single = r.denoise_guided(racc, ralb, rnd, rmom)
+            base = {"spp": spp, "frame": f, "psnr_raw": psnr_half(ref_half[f], raw),
+                    "psnr_guided": psnr_half(ref_half[f], single)}
+            for n in TEMPORAL_PRECEDING:
+                steps = frames_of(scene, cfg, sequence(f, n))
+                row = dict(base, preceding=n, subframes=len(steps[-1][0]))
+                for arm, (cp, k) in arms_of(cparams).items():
+                    h, found, clipped = accumulate(steps, cp, k)
+                    _, bgra = r.denoise_guided(h[1], h[3], h[4], h[2], gparams)
+                    row[arm] = {"psnr_temporal": psnr_half(ref_half[f], tonemapped(h[1])),
+                                "psnr_temporal_guided": psnr_half(ref_half[f], bgra), "found": found, "clipped": clipped}
+                table.append(row)
+                print(json.dumps(row), flush=True)
+            if spp == TEMPORAL_SPPS[-1]:
+                # the kernel is a fraction of a millisecond: the mean of 20 runs back to back
+                prev, _, _ = accumulate(steps[:-1], cparams, CLAMP_BLUR_CAMERAS)
+                cams, acc, mom, alb, nd = steps[-1]
+                for n_cams in CLAMP_TIMED_CAMERAS:
+                    use = (cams * n_cams)[:n_cams] if n_cams > 1 else [cams[len(cams) // 2]]
+                    for radius in (0, 1, 2):
+                        cp = TemporalClampParams.default(clamp_radius=radius)
+                        cp.clamp_sigma, cp.clipped_history = cparams.clamp_sigma, cparams.clipped_history
+                        _, ms, _ = timed(lambda: [r.temporal_accumulate_clamped(use, acc, mom, alb, nd, prev, cp)
+                                                  for _ in range(20)][-1])
+                        timing.append({"frame": f, "spp": spp, "n_cams": n_cams, "clamp_radius": radius, "ms": ms / 20})
+                _, ms, _ = timed(lambda: [r.temporal_accumulate(cams[len(cams) // 2], acc, mom, alb, nd, prev, cparams.base)
+                                          for _ in range(20)][-1])
+                timing.append({"frame": f, "spp": spp, "kernel": "k_temporal_accumulate", "ms": ms / 20})
+                print(json.dumps(timing[-10:]), flush=True)
+        scene.close()
+    result["table"] = table
+    result["kernel_ms"] = timing
+    os.makedirs(args.out, exist_ok=True)
+    dump_rows_compact(result, os.path.join(args.out, "temporal_clamp_study.json"))
+    print("wrote", os.path.join(args.out, "temporal_clamp_study.json"))
+
+
 ADAPTIVE_BUDGETS = (64, 256, 1024)
 ADAPTIVE_PASSES = 8
 ADAPTIVE_SWEEP_BUDGETS = (64, 256)
@@ -537,6 +695,7 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--guided", action="store_true")
     ap.add_argument("--temporal", action="store_true")
+    ap.add_argument("--temporal-clamp", action="store_true")
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_study"))
     args = ap.parse_args()
@@ -546,6 +705,8 @@ def main():
         return guided_study(args)
     if args.temporal:
         return temporal_study(args)
+    if args.temporal_clamp:
+        return temporal_clamp_study(args)
     r = P.GpuRenderer(0)
     result = {"config": {"width": W, "height": H, "frames": FRAMES, "reference_spp": REF_SPP},
               "device": torch.cuda.get_device_name(0)}
