@@ -15,14 +15,14 @@
 //   k_dn_demodulate<GUIDED>, k_dn_atrous<STEP>, k_dn_remodulate
 //                   the a-trous denoisers: STEP is DenoiseStep (fixed sigmas)
 //                   or DenoiseGuidedStep (variance-guided)
-//   k_temporal_accumulate  last frame's radiance and moments, reprojected
-//                   and blended with this frame's by sample count
-//   k_temporal_accumulate_clamped  the same through a list of cameras, the
-//                   history clamped to the frame's local colour range
-//   k_ad_select<ALL>, k_ad_camera, k_ad_fold, k_ad_resolve
+//   k_temporal_accumulate<CLAMPED>  last frame's radiance and moments,
+//                   reprojected and blended with this frame's by sample count;
+//                   <true> through a list of cameras, the history clamped to
+//                   the frame's local colour range
+//   k_ad_select<ALL>, k_ad_fold, k_ad_resolve
 //                   adaptive sampling (ptg_render_adaptive): the stopping rule
-//                   compacted into a pixel list, the camera kernel and the
-//                   fold over that list, the final division
+//                   compacted into a pixel list, the fold over that list, the
+//                   final division (its camera is k_wf_camera over AdaptivePass)
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
@@ -137,6 +137,8 @@ struct PixelMap {
         y = (t / tiles_x) * th + q / tw;
         return x < img_w && y < img_h;
     }
+    // local sample index -> sample index of the frame (k_wf_camera's MAP)
+    __device__ __forceinline__ uint32_t sample(uint32_t j) const { return j; }
 };
 
 // 16-byte non-temporal load / store of a float4 or uint4 record
@@ -207,8 +209,14 @@ __device__ __forceinline__ void chunk_coords(uint32_t i, uint32_t nj, uint32_t& 
 // before the fold of the chunk ahead of it has read that buffer
 // (trace_chunk_wavefront), so a dead lane's zero sample is written where the
 // dead path retires (shade_path).
-template<bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_wf_camera(DevScene sc, PixelMap pm, uint32_t j0, uint32_t nj, uint32_t M,
+// MAP says which pixels and samples the queue holds: npix queue pixels,
+// pixel(p, x, y) (false: a dead lane) and sample(j), the frame's sample index
+// of local sample j.  PixelMap: a rectangle or tile set, every sample.
+// AdaptivePass: a pass's pixel list and its strided samples; the queue
+// positions, PathSoA records and dead lanes are the same, so the walk,
+// classify, shade and sky kernels run on either queue unchanged.
+template<bool COUNT, class MAP>
+__global__ __launch_bounds__(kBlock) void k_wf_camera(DevScene sc, MAP pm, uint32_t j0, uint32_t nj, uint32_t M,
                                                       PathSoA S, uint32_t* __restrict__ counts,
                                                       unsigned long long* __restrict__ counters)
 {
@@ -228,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_camera(DevScene sc, PixelMap pm, 
             st_state(S.ray_d + i, make_float4(0.f, 0.f, 1.f, 0.f));
             continue;
         }
-        const int32_t j = (int32_t)(j0 + jj);
+        const int32_t j = (int32_t)pm.sample(j0 + jj);
         const uint8_t* sf = subframe_of(sc, j);
         u4 seed;
         f3 o, d;
@@ -745,12 +753,8 @@ template<bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_trace(DevScene sc, PixelMap pm, uint32_t j0, uint32_t nj,
                                                   float4* __restrict__ out, unsigned long long* __restrict__ counters)
 {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t wave = g >> 6, lane = g & 63u;
-    const uint32_t sgroups = (nj + 7u) >> 3;
-    const uint32_t sg = wave % sgroups, pg = wave / sgroups;
-    const uint32_t jj = sg * 8u + (lane & 7u);
-    const uint32_t p = pg * 8u + (lane >> 3);
+    uint32_t p, jj;
+    chunk_coords(blockIdx.x * blockDim.x + threadIdx.x, nj, p, jj);
     Counters cnt;
     if(p < pm.npix && jj < nj)
     {
@@ -769,6 +773,47 @@ __global__ __launch_bounds__(kBlock) void k_trace(DevScene sc, PixelMap pm, uint
 // Rec. 709 luminance of the moments and of the guided denoiser: three
 // products, two sums, each one float32 rounding
 __device__ __forceinline__ float lum709(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
+// The fold's arithmetic, each operation one float32 rounding (k_accumulate,
+// k_ad_fold, k_ad_resolve, tp_blend and ad_noisy share it).
+//
+// A chunk's nj samples of queue pixel q (npix queue pixels) added, in sample
+// order, to the running radiance sum and, with MOMENTS, to the luminance
+// moments (s1, s2, n) of the finite ones.
+template<bool MOMENTS>
+__device__ __forceinline__ void fold_samples(const float4* samples, uint32_t npix, uint32_t q, uint32_t nj,
+                                             float& ax, float& ay, float& az, float& s1, float& s2, uint32_t& n)
+{
+    for(uint32_t j = 0; j < nj; ++j)
+    {
+        const float4 s = ld_out(samples + size_t(j) * npix + q);
+        ax = ax + s.x;
+        ay = ay + s.y;
+        az = az + s.z;
+        if constexpr(MOMENTS)
+            if(finite3(V3(s.x, s.y, s.z)))
+            {
+                const float L = lum709(s.x, s.y, s.z);
+                s1 = s1 + L;
+                s2 = s2 + L * L;
+                ++n;
+            }
+    }
+}
+// the variance of the mean of n samples with the moments (m1, m2); a NaN gives 0
+__device__ __forceinline__ float var_of_mean(float m1, float m2, float n)
+{
+    const float d = m2 - m1 * m1;
+    const float var = d > 0.0f ? d : 0.0f;
+    return n >= 2.0f ? var / (n - 1.0f) : 0.0f;
+}
+// the sums (s1, s2) of n > 0 finite samples -> (m1, m2, variance of the mean, n)
+__device__ __forceinline__ float4 moments_of(float s1, float s2, uint32_t n)
+{
+    const float nf = (float)n;
+    const float m1 = s1 / nf, m2 = s2 / nf;
+    return make_float4(m1, m2, var_of_mean(m1, m2, nf), nf);
+}
 
 // acc[p] (+)= samples in index order; on the last chunk / spp and tonemap.
 // MOMENTS (ptg_render_moments): in the same pass over the chunk, the first two
@@ -797,21 +842,7 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
             s1 = m.x; s2 = m.y; n = __float_as_uint(m.z);
         }
     }
-    for(uint32_t j = 0; j < nj; ++j)
-    {
-        const float4 s = ld_out(samples + size_t(j) * pm.npix + p);
-        ax = ax + s.x;
-        ay = ay + s.y;
-        az = az + s.z;
-        if constexpr(MOMENTS)
-            if(finite3(V3(s.x, s.y, s.z)))
-            {
-                const float L = lum709(s.x, s.y, s.z);
-                s1 = s1 + L;
-                s2 = s2 + L * L;
-                ++n;
-            }
-    }
+    fold_samples<MOMENTS>(samples, pm.npix, p, nj, ax, ay, az, s1, s2, n);
     if(!last)
     {
         acc[p] = make_float4(ax, ay, az, 0.f);
@@ -825,19 +856,7 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
     const bool inside = pm.pixel(p, x, y);
     if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
-    if constexpr(MOMENTS)
-    {
-        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        if(inside && n > 0)
-        {
-            const float nf = (float)n;
-            const float m1 = s1 / nf, m2 = s2 / nf;
-            const float d = m2 - m1 * m1;
-            const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
-            r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
-        }
-        out_moments[p] = r;
-    }
+    if constexpr(MOMENTS) out_moments[p] = inside && n > 0 ? moments_of(s1, s2, n) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sample_list(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
@@ -1139,7 +1158,7 @@ __global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, 
     if(out_bgra) out_bgra[i] = tonemap(c);
 }
 
-// ---- temporal accumulation ----
+// ---- temporal accumulation (several cameras and the history clamp: 4.17) ----
 
 // The parts of a ptg_camera the reprojection reads.
 struct TemporalCam {
@@ -1147,26 +1166,24 @@ struct TemporalCam {
     f3 pos;
     float aspect, ifl, fd;
 };
+constexpr uint32_t kTemporalMaxCams = 512;  // ptg_temporal_accumulate_clamped's n_cams
+// k_temporal_accumulate's arguments.  The plain entry reads `cam` and none of
+// the clamped entry's fields; the clamped entry reads those and not `cam`.
 struct TemporalArgs {
     uint32_t w, h;
     uint32_t has_history;                  // 0: first frame, the hist_* pointers are null
     float max_history, depth_tolerance, normal_tolerance, albedo_tolerance;
-    TemporalCam cam, hist;
+    TemporalCam cam, hist;                 // plain: this frame's camera; the history's
+    uint32_t n_cams;                       // clamped: this frame's cameras, in the context's buffer
+    uint32_t clamp_radius;                 // clamped: 0: no clamp
+    float clamp_sigma, clipped_history;    // clamped
 };
-
-// the variance of the mean of n samples with the moments (m1, m2), as k_accumulate ends
-__device__ __forceinline__ float tp_var_of_mean(float m1, float m2, float n)
-{
-    const float dvar = m2 - m1 * m1;
-    const float var = dvar > 0.0f ? dvar : 0.0f;
-    return n >= 2.0f ? var / (n - 1.0f) : 0.0f;
-}
 
 // Steps 2-4 of the definition for one camera: the first-hit point of pixel
 // (x, y), from its centre ray through `cam` and the mean depth z, is
 // projected into `hist`; the four bilinear taps around it that show the same
 // surface (depth, normal, albedo) add into the seven running sums.  A camera
-// that fails a test adds nothing.  One definition for both kernels below.
+// that fails a test adds nothing.
 struct TemporalSums {
     float sw = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
 };
@@ -1252,79 +1269,43 @@ __device__ __forceinline__ void tp_blend(float hx, float hy, float hz, float h1,
         const float al = M.w / nt;
         oc = make_float4(hx + al * (R.x - hx), hy + al * (R.y - hy), hz + al * (R.z - hz), 0.0f);
         const float m1 = h1 + al * (M.x - h1), m2 = h2 + al * (M.y - h2);
-        om = make_float4(m1, m2, tp_var_of_mean(m1, m2, nt), nt);
+        om = make_float4(m1, m2, var_of_mean(m1, m2, nt), nt);
     }
     else
     {   // nothing usable in this frame: the history alone
         oc = make_float4(hx, hy, hz, 0.0f);
-        om = make_float4(h1, h2, tp_var_of_mean(h1, h2, nh), nh);
+        om = make_float4(h1, h2, var_of_mean(h1, h2, nh), nh);
     }
 }
 
 // One work-item per pixel: the pixel's first-hit point, from its centre ray
-// through `cam` and its mean depth, is projected into `hist`; the four
-// bilinear taps around it that show the same surface (depth, normal, albedo)
-// give the history's radiance and moments, which are blended with this
+// through this frame's camera and its mean depth, is projected into `hist`;
+// the four bilinear taps around it that show the same surface (depth, normal,
+// albedo) give the history's radiance and moments, which are blended with this
 // frame's by their sample counts.  Every operation is one float32 rounding in
 // the order DESIGN.md gives.  This frame's images are read at the pixel alone
 // (the outputs may be the radiance and moments themselves: no __restrict__
 // on those four); the history is gathered.
-__global__ __launch_bounds__(kBlock) void k_temporal_accumulate(TemporalArgs a, const float4* radiance, const float4* moments,
-                                                                const float4* __restrict__ albedo,
-                                                                const float4* __restrict__ normal_depth,
-                                                                const float4* __restrict__ hist_radiance,
-                                                                const float4* __restrict__ hist_moments,
-                                                                const float4* __restrict__ hist_albedo,
-                                                                const float4* __restrict__ hist_normal_depth,
-                                                                float4* out_radiance, float4* out_moments,
-                                                                uchar4* __restrict__ out_bgra)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= a.w * a.h) return;
-    const uint32_t x = i % a.w, y = i / a.w;
-    const float4 R = radiance[i], M = moments[i], A = albedo[i], G = normal_depth[i];
-    TemporalSums s;
-    const float cov = A.w;
-    if(a.has_history && cov > 0.0f)
-        tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, a.cam, a.hist, x, y, G.w / cov, A, G,
-                  hist_radiance, hist_moments, hist_albedo, hist_normal_depth);
-    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
-    if(s.sw > 0.0f)
-        tp_blend(s.cx / s.sw, s.cy / s.sw, s.cz / s.sw, s.s1 / s.sw, s.s2 / s.sw, s.sn / s.sw, a.max_history, R, M, oc, om);
-    out_radiance[i] = oc;
-    out_moments[i] = om;
-    if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
-}
-
-// ---- temporal accumulation over several cameras, with a history clamp ----
-
-constexpr uint32_t kTemporalMaxCams = 512;  // ptg_temporal_accumulate_clamped's n_cams
-struct TemporalClampArgs {
-    uint32_t w, h;
-    uint32_t has_history;                  // 0: first frame, the hist_* pointers are null
-    uint32_t n_cams;                       // this frame's cameras, in the context's buffer
-    uint32_t clamp_radius;                 // 0: no clamp
-    float max_history, depth_tolerance, normal_tolerance, albedo_tolerance;
-    float clamp_sigma, clipped_history;
-    TemporalCam hist;
-};
-
-// k_temporal_accumulate with two insertions.  The reprojection runs once per
-// camera of `cams` (a wave-uniform loop: the cameras come through scalar
-// loads) into the same seven sums, so the history of a motion-blurred pixel is
-// gathered along the blur.  With clamp_radius r > 0 the history's colour is
-// then clamped, per channel, to mean +- clamp_sigma standard deviations of the
-// finite pixels of this frame's (2r + 1)^2 window; a clipped history's first
-// moment follows the colour, its second keeps the variance, and its sample
-// count is capped at clipped_history.  `radiance` is gathered by the clamp:
-// with r > 0 it is not out_radiance (the host refuses that).  flags
-// (optional): bit 0 the pixel found history, bit 1 its history was clipped.
-__global__ __launch_bounds__(kBlock) void k_temporal_accumulate_clamped(
-    TemporalClampArgs a, const TemporalCam* __restrict__ cams, const float4* radiance, const float4* moments,
-    const float4* __restrict__ albedo, const float4* __restrict__ normal_depth, const float4* __restrict__ hist_radiance,
+//
+// The plain entry (CLAMPED = false) has one camera, a.cam in the kernel
+// arguments; `cams` and `flags` are null and never read.  The clamped entry
+// has two insertions.  The reprojection runs once per camera of `cams` (a
+// wave-uniform loop: the cameras come through scalar loads) into the same
+// seven sums, so the history of a motion-blurred pixel is gathered along the
+// blur.  With clamp_radius r > 0 the history's colour is then clamped, per
+// channel, to mean +- clamp_sigma standard deviations of the finite pixels of
+// this frame's (2r + 1)^2 window; a clipped history's first moment follows the
+// colour, its second keeps the variance, and its sample count is capped at
+// clipped_history.  `radiance` is gathered by the clamp: with r > 0 it is not
+// out_radiance (the host refuses that).  flags (optional): bit 0 the pixel
+// found history, bit 1 its history was clipped.
+template<bool CLAMPED>
+__global__ __launch_bounds__(kBlock) void k_temporal_accumulate(
+    TemporalArgs a, const float4* radiance, const float4* moments, const float4* __restrict__ albedo,
+    const float4* __restrict__ normal_depth, const float4* __restrict__ hist_radiance,
     const float4* __restrict__ hist_moments, const float4* __restrict__ hist_albedo,
     const float4* __restrict__ hist_normal_depth, float4* out_radiance, float4* out_moments, uchar4* __restrict__ out_bgra,
-    uint8_t* __restrict__ flags)
+    const TemporalCam* __restrict__ cams, uint8_t* __restrict__ flags)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= a.w * a.h) return;
@@ -1335,9 +1316,14 @@ __global__ __launch_bounds__(kBlock) void k_temporal_accumulate_clamped(
     if(a.has_history && cov > 0.0f)
     {
         const float z = G.w / cov;
-        for(uint32_t k = 0; k < a.n_cams; ++k)
-            tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, cams[k], a.hist, x, y, z, A, G,
+        auto gather = [&](const TemporalCam& cam) {
+            tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, cam, a.hist, x, y, z, A, G,
                       hist_radiance, hist_moments, hist_albedo, hist_normal_depth);
+        };
+        if constexpr(CLAMPED)
+            for(uint32_t k = 0; k < a.n_cams; ++k) gather(cams[k]);
+        else
+            gather(a.cam);   // not a one-trip loop: that compiles to 2 VGPRs more
     }
     float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
     uint32_t fl = 0;
@@ -1346,7 +1332,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal_accumulate_clamped(
         fl = 1u;
         float hc[3] = {s.cx / s.sw, s.cy / s.sw, s.cz / s.sw};
         float h1 = s.s1 / s.sw, h2 = s.s2 / s.sw, hn = s.sn / s.sw;
-        if(a.clamp_radius)
+        if(CLAMPED && a.clamp_radius)
         {
             const int32_t r = (int32_t)a.clamp_radius;
             int32_t n = 0;
@@ -1399,7 +1385,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal_accumulate_clamped(
     out_radiance[i] = oc;
     out_moments[i] = om;
     if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
-    if(flags) flags[i] = (uint8_t)fl;
+    if(CLAMPED && flags) flags[i] = (uint8_t)fl;
 }
 
 // ---- adaptive sampling ----
@@ -1410,8 +1396,17 @@ struct AdaptivePass {
     uint32_t x0, y0, w, h;          // rectangle: pixel id = row * w + column
     uint32_t passes, pass, m;       // the pass owns subframes pass, pass + passes, ...; m samples each
     const uint32_t* list;           // the active pixels' ids
-    uint32_t len;
+    uint32_t npix;                  // their number: the queue pixels of the pass
 
+    // queue pixel p -> image pixel; an id outside the rectangle is a dead lane
+    __device__ __forceinline__ bool pixel(uint32_t p, uint32_t& x, uint32_t& y) const
+    {
+        const uint32_t pix = list[p];
+        if(pix >= w * h) return false;
+        x = x0 + pix % w;
+        y = y0 + pix / w;
+        return true;
+    }
     // local sample index of the pass -> sample index of the frame
     __device__ __forceinline__ uint32_t sample(uint32_t jl) const { return ((jl / m) * passes + pass) * m + jl % m; }
 };
@@ -1423,13 +1418,9 @@ __device__ __forceinline__ bool ad_noisy(float4 mom, float threshold, float lumi
 {
     const uint32_t n = __float_as_uint(mom.z);
     if(n < 2u) return true;
-    const float nf = (float)n;
-    const float m1 = mom.x / nf, m2 = mom.y / nf;
-    const float d = m2 - m1 * m1;
-    const float var = d > 0.0f ? d : 0.0f;
-    const float vm = var / (nf - 1.0f);
-    const float tol = threshold * (m1 + luminance_floor);
-    return !(vm <= tol * tol);
+    const float4 m = moments_of(mom.x, mom.y, n);
+    const float tol = threshold * (m.x + luminance_floor);
+    return !(m.z <= tol * tol);
 }
 
 // Select and compact, one work-item per rectangle pixel: the pixel is active
@@ -1486,48 +1477,6 @@ __global__ __launch_bounds__(kBlock) void k_ad_select(uint32_t w, uint32_t h, ui
     list[pos] = p;   // pos < the number of active pixels <= npix
 }
 
-// k_wf_camera over a pixel list with the pass's strided sample map: queue
-// position, PathSoA records and dead lanes exactly as k_wf_camera writes them
-// for a map of ad.len pixels (chunk_coords: 8 list entries x 8 local samples
-// per wave), so the walk, classify, shade and sky kernels run on its queue
-// unchanged.
-template<bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_ad_camera(DevScene sc, AdaptivePass ad, uint32_t j0, uint32_t nj, uint32_t M,
-                                                      PathSoA S, uint32_t* __restrict__ counts,
-                                                      unsigned long long* __restrict__ counters)
-{
-    if(blockIdx.x == 0 && threadIdx.x == 0) counts[0] = M;
-    uint32_t lives = 0;
-    for(uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x)
-    {
-        uint32_t p, jj;
-        chunk_coords(i, nj, p, jj);
-        const bool in_chunk = p < ad.len && jj < nj;
-        const uint32_t pix = in_chunk ? ad.list[p] : 0xFFFFFFFFu;
-        const uint32_t slot = in_chunk ? jj * ad.len + p : 0xFFFFFFFFu;
-        if(!in_chunk || pix >= ad.w * ad.h)
-        {
-            st_state(S.meta + i, make_uint4(slot, META_DEAD, kBePop, 0u));   // no TLAS: the walk ends at once
-            st_state(S.ray_o + i, make_float4(0.f, 0.f, 0.f, 0.f));
-            st_state(S.ray_d + i, make_float4(0.f, 0.f, 1.f, 0.f));
-            continue;
-        }
-        const uint32_t x = ad.x0 + pix % ad.w, y = ad.y0 + pix / ad.w;
-        const int32_t j = (int32_t)ad.sample(j0 + jj);
-        const uint8_t* sf = subframe_of(sc, j);
-        u4 seed;
-        f3 o, d;
-        camera_ray(sc, sf, x, y, j, seed, o, d);
-        const uint32_t sub = (uint32_t)(sf - sc.subframes) / SF_STRIDE;
-        st_state(S.meta + i, make_uint4(slot, meta_pack(0, false, sub), sc.tlas_root[sub], 0u));
-        st_state(S.seed + i, to_uint4(seed));
-        st_state(S.ray_o + i, make_float4(o.x, o.y, o.z, 0.f));
-        st_state(S.ray_d + i, make_float4(d.x, d.y, d.z, 0.f));
-        ++lives;
-    }
-    if(COUNT) flush_counters(Counters{}, counters, lives);
-}
-
 // The fold over the list: position q adds its chunk samples, in local sample
 // order, into the running sums of the pixel it names - k_accumulate<true>'s
 // operations on acc[pixel] = (sum.xyz, samples taken as bits) and mom[pixel] =
@@ -1537,27 +1486,14 @@ __global__ __launch_bounds__(kBlock) void k_ad_fold(AdaptivePass ad, uint32_t nj
                                                     float4* __restrict__ acc, float4* __restrict__ mom)
 {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if(q >= ad.len) return;
+    if(q >= ad.npix) return;
     const uint32_t pix = ad.list[q];
     if(pix >= ad.w * ad.h) return;
     const float4 a = acc[pix], mo = mom[pix];
     float ax = a.x, ay = a.y, az = a.z;
     float s1 = mo.x, s2 = mo.y;
     uint32_t n = __float_as_uint(mo.z);
-    for(uint32_t j = 0; j < nj; ++j)
-    {
-        const float4 s = ld_out(samples + size_t(j) * ad.len + q);
-        ax = ax + s.x;
-        ay = ay + s.y;
-        az = az + s.z;
-        if(finite3(V3(s.x, s.y, s.z)))
-        {
-            const float L = lum709(s.x, s.y, s.z);
-            s1 = s1 + L;
-            s2 = s2 + L * L;
-            ++n;
-        }
-    }
+    fold_samples<true>(samples, ad.npix, q, nj, ax, ay, az, s1, s2, n);
     acc[pix] = make_float4(ax, ay, az, __uint_as_float(__float_as_uint(a.w) + nj));
     mom[pix] = make_float4(s1, s2, __uint_as_float(n), 0.f);
 }
@@ -1582,16 +1518,7 @@ __global__ __launch_bounds__(kBlock) void k_ad_resolve(uint32_t npix, const floa
     {
         const float4 mo = mom[p];
         const uint32_t n = __float_as_uint(mo.z);
-        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        if(n > 0)
-        {
-            const float nf = (float)n;
-            const float m1 = mo.x / nf, m2 = mo.y / nf;
-            const float d = m2 - m1 * m1;
-            const float var = d > 0.0f ? d : 0.0f;              // a NaN gives 0
-            r = make_float4(m1, m2, n >= 2 ? var / (nf - 1.0f) : 0.0f, nf);
-        }
-        out_moments[p] = r;
+        out_moments[p] = n > 0 ? moments_of(mo.x, mo.y, n) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if(out_samples) out_samples[p] = ns;
 }
@@ -1902,14 +1829,16 @@ int launch_plain(ptg_context* ctx, uint32_t blocks, void (*kernel)(P...), const 
     return PTG_OK;
 }
 
-// A render call's fixed parts, shared by the steps render_map is made of.
+// A render call's fixed parts, shared by the steps render_map and
+// render_adaptive are made of.
 struct RenderJob {
     ptg_context* ctx;
     const ptg_render_config* cfg;
-    PixelMap pm;
+    PixelMap pm;                           // in a pass of render_adaptive only npix counts: the list's length
     uint32_t j0, j1;                       // the sample range
     float4* out_accum;
     uchar4* out_bgra;
+    const AdaptivePass* ad = nullptr;      // render_adaptive: the pass whose list the chunks are traced and folded over
     uint32_t pipelines = 1;                // chunk pipelines (slots) in use
     uint32_t chunk = 0;                    // samples per chunk
     size_t M = 0;                          // queue positions of a full chunk
@@ -1950,7 +1879,8 @@ struct Piece { uint32_t j, n, slot; };
 // samples), each at most `target` paths.  The megakernel's target is 1 GiB of
 // per-sample results.  Wavefront chunks are as large as HBM allows, up to
 // 2^chunk_log2 paths: every bounce round then launches over a long queue, so
-// the walk and shade launches run at full occupancy with short tails.
+// the walk and shade launches run at full occupancy with short tails.  The
+// slots' buffers are then grown to that size and their state carved.
 int size_chunks(RenderJob& job, bool wf)
 {
     ptg_context* ctx = job.ctx;
@@ -1978,6 +1908,15 @@ int size_chunks(RenderJob& job, bool wf)
     job.chunk = std::min<uint32_t>(span, ((span + nchunks - 1) / nchunks + 7) & ~7u);
     job.M = job.lanes(job.chunk);
     if(job.M >= (1ull << 31)) return fail(PTG_E_RANGE, "chunk too large");
+    // the slots' buffers for chunks of that size: the samples and, wavefront, the path state
+    for(uint32_t k = 0; k < pipelines; ++k)
+    {
+        PTG_HIP(ctx->grow(ctx->slot[k].samples, size_t(job.pm.npix) * job.chunk * sizeof(float4)));
+        if(!wf) continue;
+        PTG_HIP(ctx->grow(ctx->slot[k].state, slot_state_bytes(job.M, job.rounds)));
+        if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.rounds, job.st[k]))
+            return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
+    }
     return PTG_OK;
 }
 
@@ -2001,9 +1940,9 @@ int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
 
 // One chunk of the wavefront pipeline on its slot's streams: the camera
 // kernel, then per bounce round the closest-hit walk, the shadow walk of the
-// previous round's NEE rays, classify, shade and sky.  With `ad` (a pass of
-// render_adaptive) the camera kernel is k_ad_camera over the pass's pixel
-// list, pc.j counting the pass's local samples; everything after it is the same.
+// previous round's NEE rays, classify, shade and sky.  With job.ad (a pass of
+// render_adaptive) the camera kernel runs over the pass's pixel list, pc.j
+// counting the pass's local samples; everything after it is the same.
 //
 // The hoisted camera.  `next` is the slot's next chunk of this render (null:
 // none).  With a side stream (concurrency >= 1) its camera kernel is queued
@@ -2047,9 +1986,10 @@ int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
 #ifndef PTG_CAMERAS_IN_TURN
 #define PTG_CAMERAS_IN_TURN 1
 #endif
-int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = nullptr, const AdaptivePass* ad = nullptr)
+int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = nullptr)
 {
     ptg_context* ctx = job.ctx;
+    const AdaptivePass* ad = job.ad;
     ptg_context::Slot& sl = ctx->slot[pc.slot];
     const SlotState& t = job.st[pc.slot];
     RenderJob::Cursor& at = job.cursor[pc.slot];
@@ -2081,10 +2021,10 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
     auto camera = [&](const Piece& c, hipStream_t st, uint32_t half, uint32_t* cb) -> int {
         const uint32_t M = uint32_t(job.lanes(c.n));
         PTG_HIP(hipMemsetAsync(cb, 0, kCountWords(rounds) * sizeof(uint32_t), st));
-        return ad ? launch(ctx, K_CAMERA, st, grid_of(c), 0, k_ad_camera<true>, k_ad_camera<false>, sc, *ad, c.j, c.n, M,
-                           t.S[half], cb, job.cnt_for(K_CAMERA))
-                  : launch(ctx, K_CAMERA, st, grid_of(c), 0, k_wf_camera<true>, k_wf_camera<false>, sc, job.pm, c.j, c.n, M,
-                           t.S[half], cb, job.cnt_for(K_CAMERA));
+        return ad ? launch(ctx, K_CAMERA, st, grid_of(c), 0, k_wf_camera<true, AdaptivePass>, k_wf_camera<false, AdaptivePass>,
+                           sc, *ad, c.j, c.n, M, t.S[half], cb, job.cnt_for(K_CAMERA))
+                  : launch(ctx, K_CAMERA, st, grid_of(c), 0, k_wf_camera<true, PixelMap>, k_wf_camera<false, PixelMap>, sc,
+                           job.pm, c.j, c.n, M, t.S[half], cb, job.cnt_for(K_CAMERA));
     };
     float4* out = sl.samples.as<float4>();
     const dim3 grid = grid_of(pc);
@@ -2176,7 +2116,9 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
 // stream order, with no event at all.  A render that keeps the samples'
 // moments (ptg_render_moments) folds with k_accumulate<true>, in the same
 // place and order; k_accumulate<false> touches neither ctx->mom nor the
-// null out_moments.
+// null out_moments.  A pass of render_adaptive folds with k_ad_fold over its
+// list; job.prev_slot runs through the whole render, so a pass's first fold
+// follows the last fold of the pass before it.
 int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
@@ -2186,9 +2128,12 @@ int fold_chunk(RenderJob& job, const Piece& pc)
     if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
         PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
     const auto fold = job.out_moments ? k_accumulate<true> : k_accumulate<false>;
-    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(job.pm.npix)), 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(),
-                      ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last, (float)job.cfg->samples_per_pixel,
-                      job.out_accum, job.out_bgra, job.out_moments))
+    const dim3 grid(grid_for(job.pm.npix));
+    if(int r = job.ad ? launch(ctx, K_ACCUM, as, grid, 0, k_ad_fold, k_ad_fold, *job.ad, pc.n, sl.samples.as<float4>(),
+                               ctx->acc.as<float4>(), ctx->mom.as<float4>())
+                      : launch(ctx, K_ACCUM, as, grid, 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(),
+                               ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last,
+                               (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
         return r;
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
     job.prev_slot = pc.slot;
@@ -2235,6 +2180,57 @@ int read_counters(ptg_context* ctx)
     return PTG_OK;
 }
 
+// A render's ending: a PTG_DEBUG build's tallies, a counting render's counters.
+int end_render(ptg_context* ctx)
+{
+#if PTG_DEBUG
+    if(int r = check_debug_tallies(ctx)) return r;
+#endif
+    return ctx->counting ? read_counters(ctx) : PTG_OK;
+}
+
+// A render's fixed setup: the chunk pipelines in use, the bounce rounds, a
+// counting render's counters (zeroed on the caller's stream), the scene
+// arguments and the walks' spill areas.
+int begin_render(RenderJob& job, bool wf)
+{
+    ptg_context* ctx = job.ctx;
+    job.pipelines = (wf && ctx->concurrency >= 2) ? kWfSlots : 1u;
+    job.rounds = job.cfg->max_bounces + 1;
+    job.overlap = wf && ctx->concurrency >= 1;
+    if(ctx->counting)
+    {
+        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
+        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
+        job.cnt = ctx->counters.as<unsigned long long>();
+    }
+    job.sc = ctx->scene_args(job.cfg);
+    job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
+    if(wf) PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * job.pipelines * job.spill_region) * sizeof(uint2)));
+    return PTG_OK;
+}
+
+// The other slots start after what the caller's stream holds so far: the
+// caller's own work, the zeroed counters and whatever else the render queued
+// there before its first chunk.
+int start_slots(const RenderJob& job)
+{
+    ptg_context* ctx = job.ctx;
+    if(job.pipelines < 2) return PTG_OK;
+    PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
+    for(uint32_t k = 1; k < job.pipelines; ++k)
+        PTG_HIP(hipStreamWaitEvent(ctx->slot[k].main, ctx->ev_render_start, 0));
+    return PTG_OK;
+}
+
+// The caller's stream after the render's last fold so far: it sees every chunk folded.
+int join_folds(const RenderJob& job)
+{
+    if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
+        PTG_HIP(hipStreamWaitEvent(job.ctx->stream, job.ctx->slot[job.prev_slot].ev_acc, 0));
+    return PTG_OK;
+}
+
 // Render the pixels of `pm` for samples [j0, j1): per chunk of samples, the
 // path kernels write one float4 per (pixel, sample); k_accumulate folds the
 // chunk into the running per-pixel sum in sample order.
@@ -2248,82 +2244,34 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
         return fail(PTG_E_RANGE, "the megakernel's walk stack holds " + std::to_string(PrivStack::kCap) +
                                      " entries, this frame's BVHs need " + std::to_string(ctx->stack_bound));
     RenderJob job{ctx, cfg, pm, j0, j1, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra)};
-    const uint32_t pipelines = job.pipelines = (wf && ctx->concurrency >= 2) ? kWfSlots : 1u;
-    job.rounds = cfg->max_bounces + 1;
-    job.overlap = wf && ctx->concurrency >= 1;
+    if(int r = begin_render(job, wf)) return r;
     if(int r = size_chunks(job, wf)) return r;
-    for(uint32_t k = 0; k < pipelines; ++k)
-        PTG_HIP(ctx->grow(ctx->slot[k].samples, size_t(pm.npix) * job.chunk * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
     if(out_moments)
     {
         job.out_moments = reinterpret_cast<float4*>(out_moments);
         PTG_HIP(ctx->grow(ctx->mom, size_t(pm.npix) * sizeof(float4)));
     }
-    if(ctx->counting)
-    {
-        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
-        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
-        job.cnt = ctx->counters.as<unsigned long long>();
-    }
-    if(wf)
-        for(uint32_t k = 0; k < pipelines; ++k)
-        {
-            PTG_HIP(ctx->grow(ctx->slot[k].state, slot_state_bytes(job.M, job.rounds)));
-            if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.rounds, job.st[k]))
-                return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
-        }
-    if(pipelines > 1)
-    {   // the other slots start after what the caller queued
-        PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
-        for(uint32_t k = 1; k < pipelines; ++k)
-            PTG_HIP(hipStreamWaitEvent(ctx->slot[k].main, ctx->ev_render_start, 0));
-    }
-    job.sc = ctx->scene_args(cfg);
-    job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
-    if(wf) PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * pipelines * job.spill_region) * sizeof(uint2)));
+    if(int r = start_slots(job)) return r;
     const std::vector<Piece> plan = plan_chunks(job);
     for(size_t k = 0; k < plan.size(); ++k)
     {
         const Piece& pc = plan[k];
-        const Piece* next = k + pipelines < plan.size() ? &plan[k + pipelines] : nullptr;   // the slot's next chunk
+        const Piece* next = k + job.pipelines < plan.size() ? &plan[k + job.pipelines] : nullptr;   // the slot's next chunk
         if(int r = wf ? trace_chunk_wavefront(job, pc, next) : trace_chunk_megakernel(job, pc)) return r;
         if(int r = fold_chunk(job, pc)) return r;
     }
-    if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
-        PTG_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[job.prev_slot].ev_acc, 0));   // the caller's stream sees the whole render
-#if PTG_DEBUG
-    if(int r = check_debug_tallies(ctx)) return r;
-#endif
-    return ctx->counting ? read_counters(ctx) : PTG_OK;
-}
-
-// fold_chunk for a pass of render_adaptive: k_ad_fold over the pass's list on
-// the chunk's slot stream, after the fold before it (job.prev_slot runs
-// through the whole render: a pass's first fold follows the last fold of the
-// pass before it).
-int fold_chunk_adaptive(RenderJob& job, const Piece& pc, const AdaptivePass& ad)
-{
-    ptg_context* ctx = job.ctx;
-    ptg_context::Slot& sl = ctx->slot[pc.slot];
-    const hipStream_t as = ctx->main_of(pc.slot);
-    if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
-        PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
-    if(int r = launch(ctx, K_ACCUM, as, dim3(grid_for(ad.len)), 0, k_ad_fold, k_ad_fold, ad, pc.n, sl.samples.as<float4>(),
-                      ctx->acc.as<float4>(), ctx->mom.as<float4>()))
-        return r;
-    if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
-    job.prev_slot = pc.slot;
-    return PTG_OK;
+    if(int r = join_folds(job)) return r;
+    return end_render(ctx);
 }
 
 // ptg_render_adaptive once its arguments are checked (wavefront pipeline):
 // render_map's chunk pipelines, slots and event scheme over `passes` passes of
 // N / passes samples each.  A pass traces and folds the pixels of the list in
-// ctx->ad_list (size_chunks / plan_chunks with npix = the list's length); after
-// a pass from min_passes on, k_ad_select rebuilds the list from the running
-// sums and the host reads its length - the render's only wait.  The running
-// sums are ctx->acc and ctx->mom, indexed by rectangle pixel.
+// ctx->ad_list (job.ad; size_chunks / plan_chunks with npix = the list's
+// length); after a pass from min_passes on, k_ad_select rebuilds the list from
+// the running sums and the host reads its length - the render's only wait.
+// The running sums are ctx->acc and ctx->mom, indexed by rectangle pixel.
 int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelMap& rect, const ptg_adaptive_params& P,
                     float4* out_accum, uchar4* out_bgra, float4* out_moments, uint32_t* out_samples)
 {
@@ -2331,11 +2279,7 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
     for(uint64_t& a: ctx->ad_active) a = 0;
     const uint32_t npix = rect.npix;
     if(npix == 0) return PTG_OK;
-    const uint32_t span = cfg->samples_per_pixel / P.passes;
-    RenderJob job{ctx, cfg, rect, 0, span, nullptr, nullptr};
-    const uint32_t pipelines = job.pipelines = ctx->concurrency >= 2 ? kWfSlots : 1u;
-    job.rounds = cfg->max_bounces + 1;
-    job.overlap = ctx->concurrency >= 1;
+    RenderJob job{ctx, cfg, rect, 0, cfg->samples_per_pixel / P.passes, nullptr, nullptr};
     PTG_HIP(ctx->grow(ctx->acc, size_t(npix) * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->mom, size_t(npix) * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->ad_list, size_t(npix) * sizeof(uint32_t)));
@@ -2344,54 +2288,31 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
     uint32_t* count = ctx->ad_count.as<uint32_t>();
     float4* acc = ctx->acc.as<float4>();
     float4* mom = ctx->mom.as<float4>();
-    if(ctx->counting)
-    {
-        PTG_HIP(ctx->grow(ctx->counters, kCounterWords * sizeof(unsigned long long)));
-        PTG_HIP(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
-        job.cnt = ctx->counters.as<unsigned long long>();
-    }
-    // the sums start from +0; before min_passes every pixel is active
+    if(int r = begin_render(job, true)) return r;
+    // the sums start from +0; before min_passes every pixel is active.  The
+    // other slots start behind the zeroed sums and the first list.
     PTG_HIP(hipMemsetAsync(acc, 0, size_t(npix) * sizeof(float4), ctx->stream));
     PTG_HIP(hipMemsetAsync(mom, 0, size_t(npix) * sizeof(float4), ctx->stream));
     if(int r = launch_plain(ctx, grid_for(npix), k_ad_select<true>, rect.w, rect.h, 0u, 0.0f, 0.0f, mom, list, count)) return r;
-    if(pipelines > 1)
-    {   // the other slots start after what the caller queued, the zeroed sums and the first list
-        PTG_HIP(hipEventRecord(ctx->ev_render_start, ctx->stream));
-        for(uint32_t k = 1; k < pipelines; ++k)
-            PTG_HIP(hipStreamWaitEvent(ctx->slot[k].main, ctx->ev_render_start, 0));
-    }
-    job.sc = ctx->scene_args(cfg);
-    job.spill_region = size_t(std::max(ctx->walk_grid[0], ctx->walk_grid[1])) * kBlock * ctx->stack_bound;
-    PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * pipelines * job.spill_region) * sizeof(uint2)));
-    // the caller's stream after the render's last fold so far
-    auto join_folds = [&]() -> int {
-        if(pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != 0)
-            PTG_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[job.prev_slot].ev_acc, 0));
-        return PTG_OK;
-    };
+    if(int r = start_slots(job)) return r;
     uint32_t len = npix;
+    AdaptivePass ad{rect.x0, rect.y0, rect.w, rect.h, P.passes, 0, cfg->samples_per_motion_blur_step, list, len};
+    job.ad = &ad;
     for(uint32_t k = 0; k < P.passes && len > 0; ++k)
     {
         ctx->ad_active[k] = len;
         ctx->ad_passes_run = k + 1;
-        job.pm.npix = len;
+        ad.pass = k;
+        ad.npix = job.pm.npix = len;
         if(int r = size_chunks(job, true)) return r;
-        for(uint32_t s = 0; s < pipelines; ++s)
-        {
-            PTG_HIP(ctx->grow(ctx->slot[s].samples, size_t(len) * job.chunk * sizeof(float4)));
-            PTG_HIP(ctx->grow(ctx->slot[s].state, slot_state_bytes(job.M, job.rounds)));
-            if(!carve_slot_state(ctx->slot[s].state.as<char>(), job.M, job.rounds, job.st[s]))
-                return fail(PTG_E_INVALID, "the slot state's fields do not add up to kStateBytesPerPath");
-        }
-        const AdaptivePass ad{rect.x0, rect.y0, rect.w, rect.h, P.passes, k, cfg->samples_per_motion_blur_step, list, len};
         for(const Piece& pc: plan_chunks(job))
         {
-            if(int r = trace_chunk_wavefront(job, pc, nullptr, &ad)) return r;
-            if(int r = fold_chunk_adaptive(job, pc, ad)) return r;
+            if(int r = trace_chunk_wavefront(job, pc)) return r;
+            if(int r = fold_chunk(job, pc)) return r;
         }
         if(k + 1 < P.min_passes || k + 1 >= P.passes) continue;
         // selection: every pixel of the rectangle on its current sums
-        if(int r = join_folds()) return r;
+        if(int r = join_folds(job)) return r;
         PTG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
         if(int r = launch_plain(ctx, grid_for(npix), k_ad_select<false>, rect.w, rect.h, P.dilate, P.threshold,
                                 P.luminance_floor, mom, list, count))
@@ -2400,13 +2321,10 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
         PTG_HIP(hipStreamSynchronize(ctx->stream));
         if(len > npix) return fail(PTG_E_RANGE, "ptg_render_adaptive: the active list is longer than the rectangle");
     }
-    if(int r = join_folds()) return r;
+    if(int r = join_folds(job)) return r;
     if(int r = launch_plain(ctx, grid_for(npix), k_ad_resolve, npix, acc, mom, out_accum, out_bgra, out_moments, out_samples))
         return r;
-#if PTG_DEBUG
-    if(int r = check_debug_tallies(ctx)) return r;
-#endif
-    return ctx->counting ? read_counters(ctx) : PTG_OK;
+    return end_render(ctx);
 }
 
 // What ptg_denoise and ptg_denoise_guided do once their parameters are
@@ -3128,6 +3046,60 @@ TemporalCam temporal_cam_of(const ptg_camera& c)
 
 const float4* tp_in(const ptg_float4* p) { return reinterpret_cast<const float4*>(p); }
 
+// What both temporal entries do once they have checked what is their own:
+// the common checks, the kernel's arguments, the launch.  `clamped`: the
+// clamped entry, with n_cams cameras in `cams` and every field of P; the plain
+// entry passes its one camera and P.base alone.
+int temporal_run(ptg_context* ctx, const std::string& who, bool clamped, uint32_t w, uint32_t h,
+                 const ptg_temporal_clamp_params& P, uint32_t n_cams, const ptg_camera* cams, const ptg_camera* hist_cam,
+                 const ptg_float4* radiance, const ptg_float4* moments, const ptg_float4* albedo, const ptg_float4* normal_depth,
+                 const ptg_float4* hist_radiance, const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
+                 const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra,
+                 uint8_t* out_flags)
+{
+    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
+    bool given = false, empty = false;
+    if(int r = temporal_check(who, w, h, P.base, hist_cam, hist, out_radiance, out_moments, &given, &empty)) return r;
+    if(empty) return PTG_OK;
+    TemporalArgs a;
+    a.w = w; a.h = h;
+    a.has_history = given ? 1u : 0u;
+    a.max_history = P.base.max_history;
+    a.depth_tolerance = P.base.depth_tolerance;
+    a.normal_tolerance = P.base.normal_tolerance;
+    a.albedo_tolerance = P.base.albedo_tolerance;
+    a.cam = temporal_cam_of(cams[0]);
+    a.hist = temporal_cam_of(given ? *hist_cam : cams[0]);
+    a.n_cams = n_cams;
+    a.clamp_radius = P.clamp_radius;
+    a.clamp_sigma = P.clamp_sigma;
+    a.clipped_history = P.clipped_history;
+    const TemporalCam* dev_cams = nullptr;
+    if(clamped)
+    {
+        // The cameras go through a pinned staging buffer into the context's
+        // device buffer, on the context's stream.  The device buffer is safe
+        // against reuse by stream order: the next call's copy runs behind this
+        // call's kernel.  The staging buffers alternate, and one is written again
+        // only after the copy of two calls ago that read it has completed
+        // (HostStage::reserve waits for it).
+        PTG_HIP(ctx->grow(ctx->tp_cams, size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
+        HostStage& hs = ctx->tp_stage[ctx->tp_stage_next];
+        ctx->tp_stage_next ^= 1u;
+        PTG_HIP(hs.reserve(size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
+        TemporalCam* staged = static_cast<TemporalCam*>(hs.p);
+        for(uint32_t k = 0; k < n_cams; ++k) staged[k] = temporal_cam_of(cams[k]);
+        PTG_HIP(hipMemcpyAsync(ctx->tp_cams.p, staged, size_t(n_cams) * sizeof(TemporalCam), hipMemcpyHostToDevice, ctx->stream));
+        PTG_HIP(hipEventRecord(hs.done, ctx->stream));
+        dev_cams = ctx->tp_cams.as<const TemporalCam>();
+    }
+    return launch_plain(ctx, grid_for(size_t(w) * h), clamped ? k_temporal_accumulate<true> : k_temporal_accumulate<false>, a,
+                        tp_in(radiance), tp_in(moments), tp_in(albedo), tp_in(normal_depth), tp_in(hist_radiance),
+                        tp_in(hist_moments), tp_in(hist_albedo), tp_in(hist_normal_depth),
+                        reinterpret_cast<float4*>(out_radiance), reinterpret_cast<float4*>(out_moments),
+                        reinterpret_cast<uchar4*>(out_bgra), dev_cams, out_flags);
+}
+
 } // namespace
 
 int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_params* params,
@@ -3140,25 +3112,11 @@ int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_
     if(int r = bind(ctx)) return r;
     if(!params || !cam || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
         return fail(PTG_E_INVALID, "ptg_temporal_accumulate: null argument");
-    const ptg_temporal_params P = *params;
-    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
-    bool given = false, empty = false;
-    if(int r = temporal_check("ptg_temporal_accumulate", w, h, P, hist_cam, hist, out_radiance, out_moments, &given, &empty))
-        return r;
-    if(empty) return PTG_OK;
-    TemporalArgs a;
-    a.w = w; a.h = h;
-    a.has_history = given ? 1u : 0u;
-    a.max_history = P.max_history;
-    a.depth_tolerance = P.depth_tolerance;
-    a.normal_tolerance = P.normal_tolerance;
-    a.albedo_tolerance = P.albedo_tolerance;
-    a.cam = temporal_cam_of(*cam);
-    a.hist = temporal_cam_of(given ? *hist_cam : *cam);
-    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate, a, tp_in(radiance), tp_in(moments), tp_in(albedo),
-                        tp_in(normal_depth), tp_in(hist_radiance), tp_in(hist_moments), tp_in(hist_albedo),
-                        tp_in(hist_normal_depth), reinterpret_cast<float4*>(out_radiance),
-                        reinterpret_cast<float4*>(out_moments), reinterpret_cast<uchar4*>(out_bgra));
+    ptg_temporal_clamp_params P{};   // no clamp: the kernel's plain instantiation reads the base alone
+    P.base = *params;
+    return temporal_run(ctx, "ptg_temporal_accumulate", false, w, h, P, 1, cam, hist_cam, radiance, moments, albedo, normal_depth,
+                        hist_radiance, hist_moments, hist_albedo, hist_normal_depth, out_radiance, out_moments, out_bgra,
+                        nullptr);
 }
 
 void ptg_temporal_clamp_params_default(ptg_temporal_clamp_params* p)
@@ -3191,42 +3149,8 @@ int ptg_temporal_accumulate_clamped(ptg_context* ctx, uint32_t w, uint32_t h, co
             return fail(PTG_E_INVALID, who + ": clamp_sigma and clipped_history must be positive and finite");
     if(P.clamp_radius > 0 && static_cast<const void*>(out_radiance) == static_cast<const void*>(radiance))
         return fail(PTG_E_INVALID, who + ": out_radiance is radiance, which the clamp gathers from neighbours");
-    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
-    bool given = false, empty = false;
-    if(int r = temporal_check(who, w, h, P.base, hist_cam, hist, out_radiance, out_moments, &given, &empty)) return r;
-    if(empty) return PTG_OK;
-    // The cameras go through a pinned staging buffer into the context's
-    // device buffer, on the context's stream.  The device buffer is safe
-    // against reuse by stream order: the next call's copy runs behind this
-    // call's kernel.  The staging buffers alternate, and one is written again
-    // only after the copy of two calls ago that read it has completed
-    // (HostStage::reserve waits for it).
-    const size_t bytes = size_t(n_cams) * sizeof(TemporalCam);
-    PTG_HIP(ctx->grow(ctx->tp_cams, size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
-    HostStage& hs = ctx->tp_stage[ctx->tp_stage_next];
-    ctx->tp_stage_next ^= 1u;
-    PTG_HIP(hs.reserve(size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
-    TemporalCam* staged = static_cast<TemporalCam*>(hs.p);
-    for(uint32_t k = 0; k < n_cams; ++k) staged[k] = temporal_cam_of(cams[k]);
-    PTG_HIP(hipMemcpyAsync(ctx->tp_cams.p, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    PTG_HIP(hipEventRecord(hs.done, ctx->stream));
-    TemporalClampArgs a;
-    a.w = w; a.h = h;
-    a.has_history = given ? 1u : 0u;
-    a.n_cams = n_cams;
-    a.clamp_radius = P.clamp_radius;
-    a.max_history = P.base.max_history;
-    a.depth_tolerance = P.base.depth_tolerance;
-    a.normal_tolerance = P.base.normal_tolerance;
-    a.albedo_tolerance = P.base.albedo_tolerance;
-    a.clamp_sigma = P.clamp_sigma;
-    a.clipped_history = P.clipped_history;
-    a.hist = temporal_cam_of(given ? *hist_cam : cams[0]);
-    return launch_plain(ctx, grid_for(size_t(w) * h), k_temporal_accumulate_clamped, a, ctx->tp_cams.as<const TemporalCam>(),
-                        tp_in(radiance), tp_in(moments), tp_in(albedo), tp_in(normal_depth), tp_in(hist_radiance),
-                        tp_in(hist_moments), tp_in(hist_albedo), tp_in(hist_normal_depth),
-                        reinterpret_cast<float4*>(out_radiance), reinterpret_cast<float4*>(out_moments),
-                        reinterpret_cast<uchar4*>(out_bgra), out_flags);
+    return temporal_run(ctx, who, true, w, h, P, n_cams, cams, hist_cam, radiance, moments, albedo, normal_depth, hist_radiance,
+                        hist_moments, hist_albedo, hist_normal_depth, out_radiance, out_moments, out_bgra, out_flags);
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

@@ -258,6 +258,28 @@ class GpuRenderer:
         return bgra, out
 
     # -- temporal accumulation -------------------------------------------------
+    def _temporal(self, entry, p, cams, radiance, moments, albedo, normal_depth, history, want_bgra, out_radiance,
+                  out_moments, flags=()):
+        """The two temporal entries' shared half: the images checked, the
+        outputs allocated, `entry` called with its own camera arguments
+        `cams` and, behind bgra, its own trailing `flags`."""
+        import torch
+        images = (radiance, moments, albedo, normal_depth) + (tuple(history[1:]) if history is not None else ())
+        h, w = radiance.shape[:2]
+        for t in images:
+            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
+        hc = N.Camera.of(history[0]) if history is not None else None
+        if out_radiance is None:
+            out_radiance = torch.empty_like(radiance)
+        if out_moments is None:
+            out_moments = torch.empty_like(moments)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
+        hist = images[4:] if history is not None else (None,) * 4
+        N.check(getattr(N.lib(), entry)(self._ctx, w, h, C.byref(p), *cams, C.byref(hc) if hc is not None else None,
+                                        *map(_ptr, images[:4]), *map(_ptr, hist), _ptr(out_radiance), _ptr(out_moments),
+                                        _ptr(bgra), *map(_ptr, flags)), entry)
+        return out_radiance, out_moments, bgra
+
     def temporal_accumulate(self, cam, radiance, moments, albedo, normal_depth, history=None, params=None,
                             want_bgra=False, out_radiance=None, out_moments=None):
         """ptg_temporal_accumulate over device float32 [h, w, 4] tensors:
@@ -269,25 +291,11 @@ class GpuRenderer:
         previous frame's guides.  `out_radiance` / `out_moments` may be
         `radiance` / `moments` themselves, never a history tensor.
         Asynchronous."""
-        import torch
         from .denoise import TemporalParams
         p = params if params is not None else TemporalParams.default()
-        images = (radiance, moments, albedo, normal_depth) + (tuple(history[1:]) if history is not None else ())
-        h, w = radiance.shape[:2]
-        for t in images:
-            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
         c = N.Camera.of(cam)
-        hc = N.Camera.of(history[0]) if history is not None else None
-        if out_radiance is None:
-            out_radiance = torch.empty_like(radiance)
-        if out_moments is None:
-            out_moments = torch.empty_like(moments)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
-        hist = images[4:] if history is not None else (None,) * 4
-        N.check(N.lib().ptg_temporal_accumulate(self._ctx, w, h, C.byref(p), C.byref(c), C.byref(hc) if hc is not None else None,
-                                                *map(_ptr, images[:4]), *map(_ptr, hist), _ptr(out_radiance),
-                                                _ptr(out_moments), _ptr(bgra)), "ptg_temporal_accumulate")
-        return out_radiance, out_moments, bgra
+        return self._temporal("ptg_temporal_accumulate", p, (C.byref(c),), radiance, moments, albedo, normal_depth, history,
+                              want_bgra, out_radiance, out_moments)
 
     def temporal_accumulate_clamped(self, cams, radiance, moments, albedo, normal_depth, history=None, params=None,
                                     want_bgra=False, out_radiance=None, out_moments=None, want_flags=False):
@@ -305,25 +313,12 @@ class GpuRenderer:
         import torch
         from .denoise import TemporalClampParams
         p = params if params is not None else TemporalClampParams.default()
-        images = (radiance, moments, albedo, normal_depth) + (tuple(history[1:]) if history is not None else ())
-        h, w = radiance.shape[:2]
-        for t in images:
-            assert t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.is_contiguous()
         cams = [cams[k] for k in range(len(cams))] if isinstance(cams, np.ndarray) else list(cams)
         c = (N.Camera * max(len(cams), 1))(*(N.Camera.of(cam) for cam in cams))
-        hc = N.Camera.of(history[0]) if history is not None else None
-        if out_radiance is None:
-            out_radiance = torch.empty_like(radiance)
-        if out_moments is None:
-            out_moments = torch.empty_like(moments)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=radiance.device) if want_bgra else None
-        flags = torch.empty((h, w), dtype=torch.uint8, device=radiance.device) if want_flags else None
-        hist = images[4:] if history is not None else (None,) * 4
-        N.check(N.lib().ptg_temporal_accumulate_clamped(self._ctx, w, h, C.byref(p), len(cams), c,
-                                                        C.byref(hc) if hc is not None else None, *map(_ptr, images[:4]),
-                                                        *map(_ptr, hist), _ptr(out_radiance), _ptr(out_moments), _ptr(bgra),
-                                                        _ptr(flags)), "ptg_temporal_accumulate_clamped")
-        return (out_radiance, out_moments, bgra, flags) if want_flags else (out_radiance, out_moments, bgra)
+        flags = torch.empty(radiance.shape[:2], dtype=torch.uint8, device=radiance.device) if want_flags else None
+        out = self._temporal("ptg_temporal_accumulate_clamped", p, (len(cams), c), radiance, moments, albedo, normal_depth,
+                             history, want_bgra, out_radiance, out_moments, (flags,))
+        return out + (flags,) if want_flags else out
 
     @staticmethod
     def split_flags(flags):
