@@ -326,6 +326,25 @@ int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg,
                        uint32_t sample_begin, uint32_t sample_end,
                        ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments);
 
+/* Radiance, moments and first-hit features in one pass: as if
+ * ptg_render_moments and ptg_render_features had been called with the same
+ * rectangle and sample range.  out_accum, out_bgra and out_moments (each
+ * optional) are ptg_render_moments' bits - with a null out_moments,
+ * ptg_render's; out_albedo and out_normal_depth (both required) are
+ * ptg_render_features' bits, the division by cfg->samples_per_pixel and the
+ * miss contribution included.  No arithmetic of its own is defined.  On the
+ * wavefront pipeline the features are taken from the render's own primary
+ * rays, so no second walk is made; under ptg_set_pipeline(ctx, 1) the two
+ * passes run one after the other.  A null feature output, or two outputs
+ * that are the same buffer, is PTG_E_INVALID; rectangle, sample range and
+ * configuration are checked as ptg_render checks them.  A rectangle only (no
+ * tile set).  DEVICE pointers; asynchronous on the context's stream. */
+int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg,
+                             uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                             uint32_t sample_begin, uint32_t sample_end,
+                             ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments,
+                             ptg_float4* out_albedo, ptg_float4* out_normal_depth);
+
 /* ptg_denoise with the luminance range set per pixel by the variance of the
  * pixel's mean (moments.z of ptg_render_moments) instead of a fixed
  * sigma_color: each pass prefilters the variance over 3 x 3 pixels, weighs a

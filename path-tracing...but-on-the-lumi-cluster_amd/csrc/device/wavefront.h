@@ -175,10 +175,41 @@ PTG_D uint4 to_uint4(u4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
 //
 // KIND as in hit_info: the sky kernel instantiates KIND = 2 (the path's ray
 // missed, so the path ends here), the surface kernel KIND = 1.
+//
+// FEAT (round 0 of ptg_render_with_features only): the path also stores its
+// first-hit features at its sample slot, the values k_features takes from
+// hit_info for the same ray: a surface path (albedo, 1) and (tbn.r[2], thit),
+// a miss (1, 1, 1, 0) and zeros, a dead lane zeros as for its sample.  The
+// surface store stands right behind hit_info, ahead of every rounding
+// certificate, so a path that returns SH_REDO has written its features and the
+// MathExact pass that shades it again is the plain instantiation.  The sky
+// kernel is exact by itself (no redo): a miss stores beside its sample.
 enum ShadeResult { SH_DONE = 0, SH_CONTINUE = 1, SH_REDO = 2 };
-template<bool COUNT, int KIND = 0, class MP = MathExact>
+template<bool FEAT> struct FeatOut {};     // no features: an empty argument
+template<> struct FeatOut<true> {
+    float4* albedo;        // per chunk, indexed like the samples: albedo.rgb, coverage
+    float4* normal_depth;  // normal.xyz, depth
+    uint32_t extent;       // the chunk's sample slots (PTG_DEBUG: the index is checked against it)
+};
+template<bool FEAT>
+PTG_D void store_features(const DevScene& sc, const FeatOut<FEAT>& f, uint32_t slot, float4 a, float4 n)
+{
+    if constexpr(FEAT)
+    {
+#if PTG_DEBUG
+        if(slot >= f.extent)
+        {
+            if(sc.debug) atomicAdd(sc.debug + kDebugList, 1u);
+            return;
+        }
+#endif
+        st_out(f.albedo + slot, a);
+        st_out(f.normal_depth + slot, n);
+    }
+}
+template<bool COUNT, int KIND = 0, class MP = MathExact, bool FEAT = false>
 PTG_D ShadeResult shade_path(const DevScene& sc, PathRec& p, const Hit& h, bool occluded, float4* out_samples,
-                             Counters& cnt, MP& mp)
+                             Counters& cnt, MP& mp, const FeatOut<FEAT>& feat = FeatOut<FEAT>{})
 {
     if(p.meta.y & META_DEAD)
     {   // a lane of the chunk whose pixel is not live (a partial tile): its
@@ -187,12 +218,17 @@ PTG_D ShadeResult shade_path(const DevScene& sc, PathRec& p, const Hit& h, bool 
         // retires here from round 0's sky kernel (KIND 2): its root is kBePop,
         // so its walk ends at the first step with thit = -1 and classify puts
         // it on the sky list.  Lanes outside the chunk have no sample slot.
-        if(KIND == 2 && p.meta.x != 0xFFFFFFFFu) st_out(out_samples + p.meta.x, make_float4(0.f, 0.f, 0.f, 0.f));
+        if(KIND == 2 && p.meta.x != 0xFFFFFFFFu)
+        {
+            st_out(out_samples + p.meta.x, make_float4(0.f, 0.f, 0.f, 0.f));
+            store_features(sc, feat, p.meta.x, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f));
+        }
         return SH_DONE;
     }
     const uint8_t* sf = sc.subframes + size_t(meta_sub(p.meta)) * SF_STRIDE;
     const Light L = light_of(sf);
-    const uint32_t round = meta_round(p.meta);
+    // a FEAT instantiation shades round 0 alone: the later rounds' branches drop out of it
+    const uint32_t round = FEAT ? 0u : meta_round(p.meta);
     u4 seed = to_u4(p.seed);
     if(round > 0)
     {   // end of bounce round-1: its NEE term (it reads nothing of the hit, so
@@ -202,6 +238,9 @@ PTG_D ShadeResult shade_path(const DevScene& sc, PathRec& p, const Hit& h, bool 
         p.contrib = p.contrib + p.att * nee;
     }
     HitInfo info = hit_info<COUNT, KIND>(sc, L, p.ray_o, p.ray_d, h, cnt);
+    if constexpr(FEAT && KIND != 2)   // the first hit is this one
+        store_features(sc, feat, p.meta.x, make_float4(info.albedo.x, info.albedo.y, info.albedo.z, 1.f),
+                       make_float4(info.tbn.r[2].x, info.tbn.r[2].y, info.tbn.r[2].z, info.thit));
     if(round == 0)
     {   // primary ray (path_tracer.hh:686-693)
         f3 attenuation, in_scatter;
@@ -216,6 +255,8 @@ PTG_D ShadeResult shade_path(const DevScene& sc, PathRec& p, const Hit& h, bool 
     {
         if(MP::kFast && mp.fail_mask) return SH_REDO;
         st_out(out_samples + p.meta.x, make_float4(p.contrib.x, p.contrib.y, p.contrib.z, 0.f));
+        if constexpr(FEAT && KIND == 2)   // a miss, stored where the path retires: nothing else is live here
+            store_features(sc, feat, p.meta.x, make_float4(1.f, 1.f, 1.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f));
         return SH_DONE;
     }
     // bounce `round` (path_tracer.hh:699-720): NEE setup, BSDF sample, next ray

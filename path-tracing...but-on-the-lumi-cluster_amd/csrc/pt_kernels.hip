@@ -12,6 +12,9 @@
 //   k_rays          ray_query closest hit + shadow any-hit (parity)
 //   k_tonemap, k_scatter_tiles
 //   k_features      first-hit albedo, normal and depth
+//   k_fold_features the same sums from the features round 0 of a fused render
+//                   stored per sample (ptg_render_with_features: k_wf_shade /
+//                   k_wf_sky with FEAT), folded beside k_accumulate
 //   k_dn_demodulate<GUIDED>, k_dn_atrous<STEP>, k_dn_remodulate
 //                   the a-trous denoisers: STEP is DenoiseStep (fixed sigmas)
 //                   or DenoiseGuidedStep (variance-guided)
@@ -638,12 +641,16 @@ __device__ __forceinline__ MP shading_policy(glibc::u2v* exp_tab)
 // a path whose certificate failed is listed in redo_list (its length in
 // redo_count) and shaded again by the MathExact instance, which takes
 // redo_list as its hit_list (and appends nothing to a redo list).
-template<bool COUNT, class MP>
+// FEAT: round 0 of a fused render (ptg_render_with_features); every path also
+// stores its first-hit features (shade_path).  Every other launch, the
+// MathExact pass of that round included, is the FEAT = false instantiation.
+template<bool COUNT, class MP, bool FEAT = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MP::kFast ? PTG_SHADE_WAVES : 2, 8))) void k_wf_shade(
     DevScene sc, PathSoA cur, PathSoA nxt, uint32_t* __restrict__ counts, uint32_t round, TraceOut tr,
     const uint32_t* __restrict__ hit_list, const uint32_t* __restrict__ lcounts, uint32_t* __restrict__ next_list,
     uint32_t* __restrict__ next_shadow, float4* __restrict__ out, uint32_t* __restrict__ redo_list,
-    uint32_t* __restrict__ redo_count, unsigned long long* __restrict__ counters, unsigned long long* __restrict__ redo_tally)
+    uint32_t* __restrict__ redo_count, unsigned long long* __restrict__ counters, unsigned long long* __restrict__ redo_tally,
+    FeatOut<FEAT> feat)
 {
     const uint32_t n = lcounts[0];
     Counters cnt;
@@ -666,12 +673,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MP::kFas
             Hit h;
             bool occluded;
             const uint32_t q = hit_list[i];
-            load_queued(cur, tr, q, p, h, occluded, round > 0);
+            load_queued(cur, tr, q, p, h, occluded, !FEAT && round > 0);
 #if PTG_DEBUG
             debug_check_round(sc, p.meta, round);
 #endif
             MP mp = mp0;
-            const ShadeResult res = shade_path<COUNT, 1, MP>(sc, p, h, occluded, out, cnt, mp);
+            const ShadeResult res = shade_path<COUNT, 1, MP, FEAT>(sc, p, h, occluded, out, cnt, mp, feat);
             if(MP::kFast && res == SH_REDO)
             {
                 redo_list[atomicAdd(redo_count, 1u)] = q;
@@ -715,10 +722,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MP::kFas
 // beats ocml's plus rounding certificates (MathFast: 2x the code, spills at
 // 5 waves; measured DESIGN.md section 4), so this pass is exact by itself.
 #define PTG_SKY_WAVES 5     // 96 VGPRs (10 spilled); 4 waves: 103, none - 5 measured 0.26% faster on frames 0 and 450 (profiles/r04q_tune/ab_sky5.log)
-template<bool COUNT>
+// FEAT as in k_wf_shade: a fused render's round 0 stores the miss features too.
+template<bool COUNT, bool FEAT = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PTG_SKY_WAVES, 8))) void k_wf_sky(
     DevScene sc, PathSoA cur, TraceOut tr, uint32_t round, const uint32_t* __restrict__ sky_list,
-    const uint32_t* __restrict__ lcounts, float4* __restrict__ out, unsigned long long* __restrict__ counters)
+    const uint32_t* __restrict__ lcounts, float4* __restrict__ out, unsigned long long* __restrict__ counters,
+    FeatOut<FEAT> feat)
 {
     const uint32_t n = lcounts[1];
     Counters cnt;
@@ -736,11 +745,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PTG_SKY_
         PathRec p;
         Hit h;
         bool occluded;
-        load_queued<true>(cur, tr, sky_list[i], p, h, occluded, round > 0);
+        load_queued<true>(cur, tr, sky_list[i], p, h, occluded, !FEAT && round > 0);
 #if PTG_DEBUG
         debug_check_round(sc, p.meta, round);
 #endif
-        shade_path<COUNT, 2>(sc, p, h, occluded, out, cnt, mp);
+        shade_path<COUNT, 2, MathExactLds, FEAT>(sc, p, h, occluded, out, cnt, mp, feat);
     }
     if(COUNT) flush_counters(cnt, counters, 0);
 }
@@ -857,6 +866,47 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
     if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
     if constexpr(MOMENTS) out_moments[p] = inside && n > 0 ? moments_of(s1, s2, n) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// The feature fold of a fused render (ptg_render_with_features), beside
+// k_accumulate and under its first / last protocol: the chunk's per-sample
+// features (shade_path's FEAT stores, laid out like the samples) added in
+// sample order to eight running sums per pixel, which start from +0 and carry
+// across chunks in facc ([0, npix) albedo + coverage, [npix, 2 npix) normal +
+// depth); on the last chunk each sum / spp.  Per component that is k_features'
+// arithmetic, acc = acc + v then acc / spp, so the bits are its bits.  Every
+// value is read once: non-temporal loads, as the radiance fold's.
+__global__ __launch_bounds__(kBlock) void k_fold_features(PixelMap pm, uint32_t nj, const float4* __restrict__ albedo,
+                                                          const float4* __restrict__ normal_depth,
+                                                          float4* __restrict__ facc, int first, int last, float spp,
+                                                          float4* __restrict__ out_albedo,
+                                                          float4* __restrict__ out_normal_depth)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= pm.npix) return;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), n = a;
+    if(!first)
+    {
+        a = facc[p];
+        n = facc[pm.npix + p];
+    }
+    for(uint32_t j = 0; j < nj; ++j)
+    {
+        const float4 va = ld_out(albedo + size_t(j) * pm.npix + p);
+        const float4 vn = ld_out(normal_depth + size_t(j) * pm.npix + p);
+        a.x = a.x + va.x; a.y = a.y + va.y; a.z = a.z + va.z; a.w = a.w + va.w;
+        n.x = n.x + vn.x; n.y = n.y + vn.y; n.z = n.z + vn.z; n.w = n.w + vn.w;
+    }
+    if(!last)
+    {
+        facc[p] = a;
+        facc[pm.npix + p] = n;
+        return;
+    }
+    uint32_t x, y;
+    if(!pm.pixel(p, x, y)) return;   // as k_features: a pixel outside the image is not written
+    out_albedo[p] = make_float4(a.x / spp, a.y / spp, a.z / spp, a.w / spp);
+    out_normal_depth[p] = make_float4(n.x / spp, n.y / spp, n.z / spp, n.w / spp);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sample_list(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
@@ -1615,6 +1665,7 @@ struct ptg_context {
     // render workspace
     DevBuf acc, tmp_a, tmp_b, tmp_c, counters;
     DevBuf mom;                            // ptg_render_moments: the running (s1, s2, n) per pixel, beside acc
+    DevBuf feat_acc;                       // ptg_render_with_features: the eight running feature sums per pixel (k_fold_features)
     DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
     DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
     DevBuf ad_list, ad_count;              // ptg_render_adaptive: the active pixels' ids and their number
@@ -1660,6 +1711,7 @@ struct ptg_context {
         // the events that order main and side; ev_acc: the slot's last fold done
         hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_acc = nullptr;
         DevBuf state, samples;   // path state (SlotState), the chunk's per-sample results
+        DevBuf feat;             // a fused render's per-sample features: two arrays laid out like `samples`
     };
     Slot slot[kWfSlots];
     hipStream_t main_of(uint32_t k) const { return k ? slot[k].main : stream; }
@@ -1849,6 +1901,17 @@ struct RenderJob {
     unsigned long long* cnt = nullptr;     // counting renders: the device counters
     uint32_t prev_slot = 0xFFFFFFFFu;      // the slot of the last fold
     float4* out_moments = nullptr;         // ptg_render_moments: the fold also keeps the luminance moments
+    // ptg_render_with_features on the wavefront pipeline (both or neither): round 0
+    // stores the first-hit features per sample, fold_chunk folds them too
+    float4 *out_albedo = nullptr, *out_normal_depth = nullptr;
+    bool fused() const { return out_albedo != nullptr; }
+    // slot k's per-sample feature arrays, each pm.npix * chunk entries
+    FeatOut<true> feat_of(uint32_t k) const
+    {
+        float4* base = ctx->slot[k].feat.as<float4>();
+        const size_t n = size_t(pm.npix) * chunk;
+        return FeatOut<true>{base, base + n, uint32_t(n)};
+    }
     SlotState st[kWfSlots];
     // where a slot's next wavefront chunk stands (trace_chunk_wavefront)
     struct Cursor {
@@ -1880,7 +1943,9 @@ struct Piece { uint32_t j, n, slot; };
 // per-sample results.  Wavefront chunks are as large as HBM allows, up to
 // 2^chunk_log2 paths: every bounce round then launches over a long queue, so
 // the walk and shade launches run at full occupancy with short tails.  The
-// slots' buffers are then grown to that size and their state carved.
+// slots' buffers are then grown to that size and their state carved.  A fused
+// render (RenderJob::fused) budgets 32 B more per path and grows the slots'
+// feature buffers; every other render sizes its chunks without them.
 int size_chunks(RenderJob& job, bool wf)
 {
     ptg_context* ctx = job.ctx;
@@ -1890,12 +1955,13 @@ int size_chunks(RenderJob& job, bool wf)
     {
         size_t free_b = 0, total_b = 0;
         PTG_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t per_path = kStateBytesPerPath + sizeof(float4);   // + the path's per-sample result
+        // + the path's per-sample result and, in a fused render, its two feature records
+        const size_t per_path = kStateBytesPerPath + sizeof(float4) + (job.fused() ? 2 * sizeof(float4) : 0);
         // a slot's share of HBM, but never more than what is actually free (other
         // tenants, torch's cache): buffers this context already holds count as free
         size_t held = 0;
         for(uint32_t k = 0; k < pipelines; ++k)
-            held += ctx->slot[k].state.bytes + ctx->slot[k].samples.bytes;
+            held += ctx->slot[k].state.bytes + ctx->slot[k].samples.bytes + (job.fused() ? ctx->slot[k].feat.bytes : 0);
         const size_t share = total_b / 100 * (pipelines > 2 ? ctx->hbm_pct * 2 / pipelines : ctx->hbm_pct);
         const size_t avail = (free_b + held) / 100 * 85 / pipelines;
         target = std::max<size_t>(size_t(1) << 16, std::min(size_t(1) << ctx->chunk_log2, std::min(share, avail) / per_path));
@@ -1912,6 +1978,7 @@ int size_chunks(RenderJob& job, bool wf)
     for(uint32_t k = 0; k < pipelines; ++k)
     {
         PTG_HIP(ctx->grow(ctx->slot[k].samples, size_t(job.pm.npix) * job.chunk * sizeof(float4)));
+        if(job.fused()) PTG_HIP(ctx->grow(ctx->slot[k].feat, 2 * size_t(job.pm.npix) * job.chunk * sizeof(float4)));
         if(!wf) continue;
         PTG_HIP(ctx->grow(ctx->slot[k].state, slot_state_bytes(job.M, job.rounds)));
         if(!carve_slot_state(ctx->slot[k].state.as<char>(), job.M, job.rounds, job.st[k]))
@@ -1964,7 +2031,11 @@ int trace_chunk_megakernel(RenderJob& job, const Piece& pc)
 //     is the chunk before this one, whose last sky kernel is ahead on the
 //     side stream, behind its last shade.
 //   - nothing else: not the sample buffer, which this chunk's fold has yet to
-//     read (dead lanes: shade_path), neither TraceOut set, no list.
+//     read (dead lanes: shade_path), neither TraceOut set, no list.  Nor a
+//     fused render's feature buffer (Slot::feat), for the same reason as the
+//     samples: this chunk's round 0 wrote it and this chunk's fold
+//     (k_fold_features) has yet to read it; the next chunk's features are
+//     written by its own round 0 shade and sky, behind that fold in stream order.
 // The side stream also waits here for what main has queued so far: in a
 // render's first chunk with rounds < 2 nothing else orders it behind the
 // caller's upload of the frame the camera reads.
@@ -2027,6 +2098,8 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
                            job.pm, c.j, c.n, M, t.S[half], cb, job.cnt_for(K_CAMERA));
     };
     float4* out = sl.samples.as<float4>();
+    const bool feat0 = job.fused();
+    const FeatOut<true> feat = feat0 ? job.feat_of(pc.slot) : FeatOut<true>{nullptr, nullptr, 0u};
     const dim3 grid = grid_of(pc);
     if(!at.camera_queued)
     {
@@ -2085,12 +2158,19 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
             return e;
         // the certified pass, then the exact pass over the paths it listed: one timed interval
         if(int e = timed_begin(ctx, K_SHADE, ms)) return e;
-        launch_counted(ctx, ms, grid, 0, k_wf_shade<true, ShadeMath>, k_wf_shade<false, ShadeMath>, sc, cur, nxt, counts, r, tr,
-                       t.hit_list, lc, nee_next, shadow_next, out, t.redo_hit, rc, job.cnt_for(K_SHADE), job.redo_tally());
+        // round 0 of a fused render: the instantiations that store the first-hit features too
+        if(feat0 && r == 0)
+            launch_counted(ctx, ms, grid, 0, k_wf_shade<true, ShadeMath, true>, k_wf_shade<false, ShadeMath, true>, sc, cur, nxt,
+                           counts, r, tr, t.hit_list, lc, nee_next, shadow_next, out, t.redo_hit, rc, job.cnt_for(K_SHADE),
+                           job.redo_tally(), feat);
+        else
+            launch_counted(ctx, ms, grid, 0, k_wf_shade<true, ShadeMath>, k_wf_shade<false, ShadeMath>, sc, cur, nxt, counts, r,
+                           tr, t.hit_list, lc, nee_next, shadow_next, out, t.redo_hit, rc, job.cnt_for(K_SHADE),
+                           job.redo_tally(), FeatOut<false>{});
         if constexpr(ShadeMath::kFast)
             launch_counted(ctx, ms, dim3(kRedoGrid), 0, k_wf_shade<true, MathExact>, k_wf_shade<false, MathExact>, sc, cur, nxt,
                            counts, r, tr, t.redo_hit, rc, nee_next, shadow_next, out, nullptr, nullptr, job.cnt_for(K_SHADE),
-                           nullptr);
+                           nullptr, FeatOut<false>{});
         PTG_HIP(hipGetLastError());
         if(int e = timed_end(ctx, ms)) return e;
         // escaped rays retire without feeding the next round: their
@@ -2098,8 +2178,10 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
         // the next round's latency-bound walks (started beside shade instead,
         // the two compete for registers: 9% slower on frame 0)
         if(int e = side_after_main()) return e;
-        if(int e = launch(ctx, K_SKY, ss, grid, 0, k_wf_sky<true>, k_wf_sky<false>, sc, cur, tr, r, t.sky_list, lc, out,
-                          job.cnt_for(K_SHADE)))
+        if(int e = feat0 && r == 0 ? launch(ctx, K_SKY, ss, grid, 0, k_wf_sky<true, true>, k_wf_sky<false, true>, sc, cur, tr, r,
+                                            t.sky_list, lc, out, job.cnt_for(K_SHADE), feat)
+                                   : launch(ctx, K_SKY, ss, grid, 0, k_wf_sky<true>, k_wf_sky<false>, sc, cur, tr, r, t.sky_list,
+                                            lc, out, job.cnt_for(K_SHADE), FeatOut<false>{}))
             return e;
     }
     return main_after_side();   // join before the fold
@@ -2116,9 +2198,11 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
 // stream order, with no event at all.  A render that keeps the samples'
 // moments (ptg_render_moments) folds with k_accumulate<true>, in the same
 // place and order; k_accumulate<false> touches neither ctx->mom nor the
-// null out_moments.  A pass of render_adaptive folds with k_ad_fold over its
-// list; job.prev_slot runs through the whole render, so a pass's first fold
-// follows the last fold of the pass before it.
+// null out_moments.  A fused render (ptg_render_with_features) folds the
+// chunk's features with k_fold_features right behind it, ahead of the event:
+// the feature sums follow the same chain.  A pass of render_adaptive folds
+// with k_ad_fold over its list; job.prev_slot runs through the whole render,
+// so a pass's first fold follows the last fold of the pass before it.
 int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
@@ -2135,6 +2219,14 @@ int fold_chunk(RenderJob& job, const Piece& pc)
                                ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last,
                                (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
         return r;
+    if(job.fused())
+    {   // the features of the chunk, directly behind its samples: same stream, same order, same event
+        const FeatOut<true> f = job.feat_of(pc.slot);
+        if(int r = launch(ctx, K_ACCUM, as, grid, 0, k_fold_features, k_fold_features, job.pm, pc.n, f.albedo, f.normal_depth,
+                          ctx->feat_acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel, job.out_albedo,
+                          job.out_normal_depth))
+            return r;
+    }
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
     job.prev_slot = pc.slot;
     return PTG_OK;
@@ -2234,8 +2326,12 @@ int join_folds(const RenderJob& job)
 // Render the pixels of `pm` for samples [j0, j1): per chunk of samples, the
 // path kernels write one float4 per (pixel, sample); k_accumulate folds the
 // chunk into the running per-pixel sum in sample order.
+// With out_albedo / out_normal_depth (wavefront only: ptg_render_with_features)
+// round 0 also stores every sample's first-hit features and k_fold_features
+// folds them.
 int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
-               ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments = nullptr)
+               ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments = nullptr,
+               ptg_float4* out_albedo = nullptr, ptg_float4* out_normal_depth = nullptr)
 {
     if(pm.npix == 0) return PTG_OK;
     if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
@@ -2244,9 +2340,16 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
         return fail(PTG_E_RANGE, "the megakernel's walk stack holds " + std::to_string(PrivStack::kCap) +
                                      " entries, this frame's BVHs need " + std::to_string(ctx->stack_bound));
     RenderJob job{ctx, cfg, pm, j0, j1, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra)};
+    if(out_albedo && out_normal_depth)
+    {
+        if(!wf) return fail(PTG_E_INVALID, "render_map: fused features run on the wavefront pipeline");
+        job.out_albedo = reinterpret_cast<float4*>(out_albedo);
+        job.out_normal_depth = reinterpret_cast<float4*>(out_normal_depth);
+    }
     if(int r = begin_render(job, wf)) return r;
     if(int r = size_chunks(job, wf)) return r;
     PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
+    if(job.fused()) PTG_HIP(ctx->grow(ctx->feat_acc, 2 * size_t(pm.npix) * sizeof(float4)));
     if(out_moments)
     {
         job.out_moments = reinterpret_cast<float4*>(out_moments);
@@ -2920,6 +3023,29 @@ int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t
     sc.spill = ctx->feat_spill.as<uint2>();
     return launch_plain(ctx, grid, k_features, sc, pm, sample_begin, sample_end, (float)cfg->samples_per_pixel,
                         reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth));
+}
+
+int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                             uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_accum, ptg_uchar4* out_bgra,
+                             ptg_float4* out_moments, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, sample_end)) return r;
+    if(!out_albedo || !out_normal_depth) return fail(PTG_E_INVALID, "ptg_render_with_features: null feature output");
+    const void* outs[5] = {out_accum, out_bgra, out_moments, out_albedo, out_normal_depth};
+    for(int a = 0; a < 5; ++a)
+        for(int b = a + 1; b < 5; ++b)
+            if(outs[a] && outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_render_with_features: two outputs are the same buffer");
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
+    if(pm.npix == 0) return PTG_OK;
+    if(sample_end <= sample_begin) return fail(PTG_E_INVALID, "empty sample range");
+    if(ctx->pipeline != 0)
+    {   // the megakernel keeps no path state between kernels: the two passes, one after the other
+        if(int r = render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments)) return r;
+        return ptg_render_features(ctx, cfg, x0, y0, w, h, sample_begin, sample_end, out_albedo, out_normal_depth);
+    }
+    return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments, out_albedo, out_normal_depth);
 }
 
 void ptg_denoise_params_default(ptg_denoise_params* p)

@@ -137,6 +137,7 @@ def lib():
         "ptg_denoise_params_default": (None, [P]),
         "ptg_denoise": (I, [P, U32, U32, P, P, P, P, P, P]),
         "ptg_render_moments": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P]),
+        "ptg_render_with_features": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P, P, P]),
         "ptg_denoise_guided_params_default": (None, [P]),
         "ptg_denoise_guided": (I, [P, U32, U32, P, P, P, P, P, P, P]),
         "ptg_temporal_params_default": (None, [P]),

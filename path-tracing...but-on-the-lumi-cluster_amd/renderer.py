@@ -178,11 +178,34 @@ class GpuRenderer:
         p = params if params is not None else DenoiseParams.default()
         return self._denoise("ptg_denoise", p, (radiance, albedo, normal_depth), want_bgra, out_radiance)
 
-    def render_denoised(self, cfg: N.RenderConfig, params=None):
+    def render_with_features(self, cfg: N.RenderConfig, rect=None, samples=None, want_moments=True):
+        """render_moments (without `want_moments`: render) and render_features
+        in one pass (ptg_render_with_features): (bgra, accum, moments or None,
+        albedo+coverage, normal+depth), each with the bits the separate calls
+        give.  On the wavefront pipeline the features come from the render's
+        own primary rays, so no second walk is made.  Asynchronous."""
+        import torch
+        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
+        dev = torch.device("cuda", self.device)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        accum, albedo, normal_depth = (torch.empty((h, w, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if want_moments else None
+        N.check(N.lib().ptg_render_with_features(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(accum), _ptr(bgra),
+                                                 _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
+                "ptg_render_with_features")
+        return bgra, accum, moments, albedo, normal_depth
+
+    def render_denoised(self, cfg: N.RenderConfig, params=None, fused=True):
         """render + render_features + denoise of the whole image: (bgra,
-        denoised radiance).  Asynchronous."""
-        _, acc = self.render(cfg, want_accum=True)
-        albedo, normal_depth = self.render_features(cfg)
+        denoised radiance).  `fused` (the default) takes the radiance and the
+        features from one render_with_features pass; fused=False makes the
+        two calls: the same bits.  Asynchronous."""
+        if fused:
+            _, acc, _, albedo, normal_depth = self.render_with_features(cfg, want_moments=False)
+        else:
+            _, acc = self.render(cfg, want_accum=True)
+            albedo, normal_depth = self.render_features(cfg)
         out, bgra = self.denoise(acc, albedo, normal_depth, params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
@@ -212,11 +235,15 @@ class GpuRenderer:
         p = params if params is not None else DenoiseGuidedParams.default()
         return self._denoise("ptg_denoise_guided", p, (radiance, albedo, normal_depth, moments), want_bgra, out_radiance)
 
-    def render_denoised_guided(self, cfg: N.RenderConfig, params=None):
+    def render_denoised_guided(self, cfg: N.RenderConfig, params=None, fused=True):
         """render_moments + render_features + denoise_guided of the whole
-        image: (bgra, denoised radiance).  Asynchronous."""
-        _, acc, moments = self.render_moments(cfg, want_accum=True)
-        albedo, normal_depth = self.render_features(cfg)
+        image: (bgra, denoised radiance).  `fused` as for render_denoised.
+        Asynchronous."""
+        if fused:
+            _, acc, moments, albedo, normal_depth = self.render_with_features(cfg)
+        else:
+            _, acc, moments = self.render_moments(cfg, want_accum=True)
+            albedo, normal_depth = self.render_features(cfg)
         out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
@@ -476,6 +503,12 @@ class TemporalDenoiser:
     whose sample count varies per pixel, as they are.  None (the default)
     renders with render_moments.
 
+    ``fused`` (default True): a step that renders with render_moments takes
+    the moments and the features from one render_with_features pass; False
+    makes the two calls, render_moments then render_features: the same bits.
+    An adaptive step always makes two calls (its pixels take different sample
+    counts, the features every sample).
+
     ``clamp_params`` / ``blur_cameras``: with both at their defaults (None, 1)
     the step accumulates with temporal_accumulate, as above.  A
     ``denoise.TemporalClampParams`` as ``clamp_params`` makes it call
@@ -490,7 +523,7 @@ class TemporalDenoiser:
     frame's middle subframe camera."""
 
     def __init__(self, renderer: GpuRenderer, cfg: N.RenderConfig, temporal_params=None, guided_params=None,
-                 seed_stride=1, adaptive_params=None, clamp_params=None, blur_cameras=1):
+                 seed_stride=1, adaptive_params=None, clamp_params=None, blur_cameras=1, fused=True):
         if clamp_params is not None and temporal_params is not None:
             raise ValueError("clamp_params.base holds the accumulation's parameters: pass no temporal_params beside it")
         if int(blur_cameras) < 1:
@@ -502,6 +535,7 @@ class TemporalDenoiser:
         self.adaptive_params = adaptive_params
         self.clamp_params = clamp_params
         self.blur_cameras = int(blur_cameras)
+        self.fused = bool(fused)
         self.seed_stride = int(seed_stride)
         self.reset()
 
@@ -522,17 +556,22 @@ class TemporalDenoiser:
         k = min(self.blur_cameras, count)
         return [((2 * j + 1) * count) // (2 * k) for j in range(k)]
 
-    def step(self, scene: N.Scene):
+    def step(self, scene: N.Scene, fused=None):
+        """The next frame; `fused` overrides the constructor's for this step."""
         r = self.renderer
+        fused = self.fused if fused is None else bool(fused)
         cfg = self.frame_config()
         r.upload(scene)
         subframes = scene.view()["subframes"]
         cam = N.Camera.of(subframes[len(subframes) // 2]["cam"])
-        if self.adaptive_params is not None:
-            _, acc, moments, _ = r.render_adaptive(cfg, self.adaptive_params)
+        if self.adaptive_params is None and fused:
+            _, acc, moments, albedo, normal_depth = r.render_with_features(cfg)
         else:
-            _, acc, moments = r.render_moments(cfg, want_accum=True)
-        albedo, normal_depth = r.render_features(cfg)
+            if self.adaptive_params is not None:
+                _, acc, moments, _ = r.render_adaptive(cfg, self.adaptive_params)
+            else:
+                _, acc, moments = r.render_moments(cfg, want_accum=True)
+            albedo, normal_depth = r.render_features(cfg)
         if self.clamp_params is None and self.blur_cameras == 1:
             # in place: this frame's radiance and moments become the accumulated ones
             acc, moments, _ = r.temporal_accumulate(cam, acc, moments, albedo, normal_depth, self.history,

@@ -58,7 +58,15 @@ remedies and uses the best row; the library's defaults
 (ptg_temporal_clamp_params_default) are the best row of the recorded sweep.
 Writes <out>/temporal_clamp_study.json.
 
-Usage: python tools/denoise_study.py [--guided | --temporal | --temporal-clamp | --adaptive] [--sweep] [--out profiles/<name>]
+--fused studies ptg_render_with_features (radiance, moments and features in
+one pass) against the two calls it replaces: frames 0 and 450 at 8 and 256
+spp, with --sweep at every sample count from 8 to 256; per row the HIP-event
+times of render_moments, render_features, the two back to back and
+render_with_features (the second of two runs each), what the fused pass costs
+over render_moments and saves against the two calls, and whether all five
+outputs had the two calls' bits.  Writes <out>/fused_study.json.
+
+Usage: python tools/denoise_study.py [--guided | --temporal | --temporal-clamp | --adaptive | --fused] [--sweep] [--out profiles/<name>]
 Writes <out>/denoise_study.json.
 """
 import argparse
@@ -690,8 +698,49 @@ def adaptive_study(args):
     print("wrote", os.path.join(args.out, "adaptive_study.json"))
 
 
+FUSED_SPPS = (8, 256)
+
+
+def fused_study(args):
+    """ptg_render_with_features against the two-call route it replaces: per
+    (spp, frame) the HIP-event times of render_moments, render_features, the
+    two back to back and render_with_features, and whether all five outputs
+    of the fused call had the two calls' bits."""
+    r = P.GpuRenderer(0)
+    result = {"config": {"width": W, "height": H, "frames": FRAMES}, "device": torch.cuda.get_device_name(0)}
+    table = []
+    first = True
+    for spp in (SPPS if args.sweep else FUSED_SPPS):
+        cfg = N.RenderConfig.make(W, H, spp)
+        scene = N.Scene(ASSETS, cfg)
+        for f in FRAMES:
+            scene.setup_frame(f)
+            r.upload(scene, include_static=first)
+            first = False
+            (bgra, acc, mom), moments_ms, _ = timed(lambda: r.render_moments(cfg, want_accum=True))
+            (alb, nd), features_ms, _ = timed(lambda: r.render_features(cfg))
+            _, both_ms, _ = timed(lambda: (r.render_moments(cfg, want_accum=True), r.render_features(cfg)))
+            fused, fused_ms, _ = timed(lambda: r.render_with_features(cfg))
+            same = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+                       for a, b in zip(fused, (bgra, acc, mom, alb, nd)))
+            row = {"spp": spp, "frame": f, "render_moments_ms": moments_ms, "render_features_ms": features_ms,
+                   "two_calls_ms": both_ms, "render_with_features_ms": fused_ms,
+                   "fused_over_moments_ms": fused_ms - moments_ms, "saved_ms": both_ms - fused_ms,
+                   "saved_share_of_features": (both_ms - fused_ms) / features_ms, "outputs_equal_bits": same}
+            table.append(row)
+            print(json.dumps(row), flush=True)
+        scene.close()
+    result["table"] = table
+    result["all_outputs_equal_bits"] = all(row["outputs_equal_bits"] for row in table)
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "fused_study.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", os.path.join(args.out, "fused_study.json"))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fused", action="store_true")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--guided", action="store_true")
     ap.add_argument("--temporal", action="store_true")
@@ -699,6 +748,8 @@ def main():
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_study"))
     args = ap.parse_args()
+    if args.fused:
+        return fused_study(args)
     if args.adaptive:
         return adaptive_study(args)
     if args.guided:

@@ -23,9 +23,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 KERNELS = {"extend": "k_wf_walk<false, false>", "shadow": "k_wf_walk<true, false>",
-           "shade": "k_wf_shade<false, ptg::dm::MathFast>", "shade_exact": "k_wf_shade<false, ptg::dm::MathExact>",
+           "shade": "k_wf_shade<false, ptg::dm::MathFast, false>",
+           "shade_exact": "k_wf_shade<false, ptg::dm::MathExact, false>",
            "camera": "k_wf_camera<false, ", "accumulate": "k_accumulate<false>", "megakernel": "k_trace<false>",
-           "sky": "k_wf_sky<false>", "classify": "k_wf_classify"}
+           "sky": "k_wf_sky<false, false>", "classify": "k_wf_classify"}
 
 
 def derive(avg, trace_avg_ns):

@@ -2,7 +2,8 @@
 import os, sys
 p = sys.argv[1] + "/pt_kernels.hip"
 s = open(p).read()
-a = """    uint32_t* __restrict__ redo_count, unsigned long long* __restrict__ counters, unsigned long long* __restrict__ redo_tally)
+a = """    uint32_t* __restrict__ redo_count, unsigned long long* __restrict__ counters, unsigned long long* __restrict__ redo_tally,
+    FeatOut<FEAT> feat)
 {
 """
 assert a in s
