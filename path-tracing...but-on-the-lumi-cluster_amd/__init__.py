@@ -4,8 +4,10 @@ Kalache-abdesattar/Path-Tracing...but-on-the-LUMI-cluster.
 Registered as ``ptlumi`` by ``ptlumi_loader`` (the directory name is not a
 Python identifier).  Layout:
 
-  csrc/            HIP kernels (csrc/pt_kernels.hip, csrc/device/) and the
-                   host C++ scene restatement (csrc/host/) -> _build/libptg.so
+  csrc/            three HIP units over csrc/runtime.h and csrc/device/ - the
+                   path tracer (pt_kernels.hip), the image-space filters
+                   (image_ops.hip), the upload (upload.hip) - and the host
+                   C++ scene restatement (csrc/host/) -> _build/libptg.so
   native.py        ctypes binding of include/ptg.h
   renderer.py      GpuRenderer: upload + render through the C ABI;
                    TemporalDenoiser: a frame sequence through the temporal

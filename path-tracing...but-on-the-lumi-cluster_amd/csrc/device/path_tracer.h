@@ -7,7 +7,8 @@
 //                        wave that sit in different levels still step
 //                        together (no nested per-level loops to diverge in).
 //   path_trace_sample()  path_trace_pixel (path_tracer.hh:637-741).
-//   tonemap()            tonemap_pixel (path_tracer.hh:753-771).
+//   (tonemap() - tonemap_pixel, path_tracer.hh:753-771 - and finite3() are in
+//   image_math.h, which the image-space unit includes without this file.)
 //
 // Results are bit-identical to the reference's C++ evaluated in IEEE
 // arithmetic (oracle/pt_oracle.c): every float/double expression below keeps
@@ -15,6 +16,7 @@
 #pragma once
 #include "layout.h"
 #include "ref_math.h"
+#include "image_math.h"
 
 namespace ptg {
 namespace dm {
@@ -62,7 +64,6 @@ struct Hit {
 // the walk's reciprocals via rcp_rn (== 1.0f / x for every x, ref_math.h)
 PTG_D float wrcp(float x) { return rcp_rn(x); }
 PTG_D float rcp_or_big(float d) { return d == 0 ? __builtin_inff() : wrcp(d); }   // 1/d, 0 -> (float)1e40
-PTG_D bool finite3(f3 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
 PTG_D uint32_t octant(f3 d) { return (d.x > 0 ? 1u : 0u) | (d.y > 0 ? 2u : 0u) | (d.z > 0 ? 4u : 0u); }
 
 // ray_triangle_intersection (math.hh:358-401) followed by the distance test of
@@ -1874,22 +1875,6 @@ PTG_D f3 path_trace_sample(const SC& sc, uint32_t px, uint32_t py, int32_t sampl
         bounce_tail(seed, L, ray_o, ray_dir, info, batt, bpdf, attenuation, contribution, regularization, mx);
     }
     return contribution;
-}
-
-// tonemap_pixel (:753-771): ACES fit, sRGB curve, clamp, BGRA
-PTG_D float aces(float c) { return (c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f); }
-PTG_D float srgb(float c)
-{
-    return c < 0.0031308f ? c * 12.92f
-                          : (float)(dpow((double)c, (double)(1.0f / 2.4f)) * (double)1.055f - (double)0.055f);
-}
-PTG_D uchar4 tonemap(f3 c)
-{
-    const float r = clampf(srgb(aces(c.x)), 0.0f, 1.0f);
-    const float g = clampf(srgb(aces(c.y)), 0.0f, 1.0f);
-    const float b = clampf(srgb(aces(c.z)), 0.0f, 1.0f);
-    return make_uchar4((unsigned char)roundf(b * 255.0f), (unsigned char)roundf(g * 255.0f),
-                       (unsigned char)roundf(r * 255.0f), 255);
 }
 
 } // namespace dm

@@ -1,7 +1,11 @@
-// HIP kernels + C ABI of the GPU renderer (include/ptg.h).
+// The path tracer: its HIP kernels, the render driver, the context's life
+// cycle and knobs, and their part of the C ABI (include/ptg.h).  The
+// image-space filters are image_ops.hip, the scene and frame upload is
+// upload.hip; runtime.h holds what the three share.
 //
-//   k_pack_tris     indices + positions -> TriRec (48 B / triangle), + vertex attributes -> TriShade (128 B)
-//   (BVH blocks are packed on the host, host/block_bvh.cpp)
+//   k_wf_camera<COUNT, MAP>, k_wf_walk<ANY, COUNT>, k_wf_classify,
+//   k_wf_shade<COUNT, MP, FEAT>, k_wf_sky<COUNT, FEAT>
+//                   the wavefront pipeline (device/wavefront.h)
 //   k_trace         path_trace_pixel for a (pixel set x sample chunk) grid,
 //                   one work-item per (pixel, sample); results to a
 //                   [sample][pixel] float4 buffer in HBM
@@ -10,18 +14,12 @@
 //                   <true> keeps the samples' luminance moments too
 //   k_sample_list   path_trace_pixel for an explicit (x, y, j) list (parity)
 //   k_rays          ray_query closest hit + shadow any-hit (parity)
-//   k_tonemap, k_scatter_tiles
+//   k_camera_rays   camera_ray's first ray per (pixel, sample) (parity)
+//   k_scatter_tiles
 //   k_features      first-hit albedo, normal and depth
 //   k_fold_features the same sums from the features round 0 of a fused render
 //                   stored per sample (ptg_render_with_features: k_wf_shade /
 //                   k_wf_sky with FEAT), folded beside k_accumulate
-//   k_dn_demodulate<GUIDED>, k_dn_atrous<STEP>, k_dn_remodulate
-//                   the a-trous denoisers: STEP is DenoiseStep (fixed sigmas)
-//                   or DenoiseGuidedStep (variance-guided)
-//   k_temporal_accumulate<CLAMPED>  last frame's radiance and moments,
-//                   reprojected and blended with this frame's by sample count;
-//                   <true> through a list of cameras, the history clamped to
-//                   the frame's local colour range
 //   k_ad_select<ALL>, k_ad_fold, k_ad_resolve
 //                   adaptive sampling (ptg_render_adaptive): the stopping rule
 //                   compacted into a pixel list, the fold over that list, the
@@ -29,93 +27,30 @@
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
-#include <hip/hip_runtime.h>
-#include "ptg.h"
-#include "device/layout.h"
+#include "runtime.h"
+#include "device/image_math.h"
 #include "device/path_tracer.h"
 #include "device/wavefront.h"
 #include "ptg_device.h"   // ptg_device_selftest, compiled here with the library's own flags (ptg_arith_selftest)
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <string>
 #include <type_traits>
-#include <vector>
 #include <unordered_map>
-#include "host/block_bvh.h"
-#include <vector>
-
-namespace ptg {
-void set_last_error(const std::string& msg);   // scene.cpp
-}
 
 using namespace ptg;
 using namespace ptg::dm;
 
 namespace {
 
-constexpr int kBlock = 256;
 #define PTG_SHADE_WAVES 3   // the certified pass (MathFast): 168 VGPRs, 6 spilled; the exact pass runs at 2
 // the surface pass's math: MathFast (certified ocml + the exact redo pass) or
 // MathExactLds (glibc's algorithms directly, no redo)
 using ShadeMath = MathFast;
 
 // ---------------------------------------------------------------- kernels --
-
-// The aperture polygon's vertex directions of every subframe (regular_polygon,
-// path_tracer.hh:50-62): (sin, cos) of side_radians * k + angle for
-// k = 0 .. sides + 1.  A polygon has few vertices and every sample's camera
-// ray uses two of them, so the camera kernel reads them instead of making
-// four double-precision trig calls.  One thread per (subframe, k).
-__global__ void k_polygon_table(const uint8_t* __restrict__ subframes, uint32_t count, float2* __restrict__ out)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if(t >= count * kPolyStride) return;
-    const uint32_t i = t / kPolyStride, k = t % kPolyStride;
-    const uint8_t* cam = subframes + size_t(i) * SF_STRIDE + SF_CAM;
-    const int32_t sides = (int32_t)rd_u(cam, 80);
-    f2 v{0.0f, 0.0f};
-    if(sides > 3 && (uint32_t)sides <= kPolyMaxSides && k <= (uint32_t)sides + 1u)
-        v = polygon_vertex(rd_f(cam, 76), (uint32_t)sides, (float)k);
-    out[t] = make_float2(v.x, v.y);
-}
-
-// one thread per triangle of each new mesh: its TriRec (positions) and its
-// TriShade (normals, albedos, materials), both at index_offset / 3 + t
-__global__ void k_pack_tris(const uint32_t* __restrict__ indices, const float4* __restrict__ pos, TriRec* __restrict__ out,
-                            const MeshJob* __restrict__ jobs, const float4* __restrict__ normal,
-                            const float4* __restrict__ albedo, const float4* __restrict__ material,
-                            TriShade* __restrict__ shade)
-{
-    const MeshJob j = jobs[blockIdx.y];
-    for(uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < j.triangle_count; t += gridDim.x * blockDim.x)
-    {
-        const uint32_t* tri = indices + j.index_offset + 3u * t;
-        const float4 a = pos[j.base_vertex_offset + tri[0]];
-        const float4 b = pos[j.base_vertex_offset + tri[1]];
-        const float4 c = pos[j.base_vertex_offset + tri[2]];
-        TriRec r;
-        r.p0x = a.x; r.p0y = a.y; r.p0z = a.z; r.p1x = b.x;
-        r.p1y = b.y; r.p1z = b.z; r.p2x = c.x; r.p2y = c.y;
-        r.p2z = c.z; r.pad0 = 0; r.pad1 = 0; r.pad2 = 0;
-        out[j.index_offset / 3u + t] = r;
-        TriShade sh;
-        for(int k = 0; k < 3; ++k)
-        {
-            const uint32_t v = j.base_vertex_offset + tri[k];
-            const float4 n = normal[v], a = albedo[v], m = material[v];
-            float* g = sh.v + 10 * k;
-            g[0] = n.x; g[1] = n.y; g[2] = n.z;
-            g[3] = a.x; g[4] = a.y; g[5] = a.z;
-            g[6] = m.x; g[7] = m.y; g[8] = m.z; g[9] = m.w;
-        }
-        sh.v[30] = sh.v[31] = 0.0f;
-        shade[j.index_offset / 3u + t] = sh;
-    }
-}
 
 // Which image pixels a launch covers: a rectangle, or an interleaved tile set.
 struct PixelMap {
@@ -182,7 +117,6 @@ __device__ __forceinline__ void flush_counters(const Counters& c, unsigned long 
 // Counting builds: paths the MathFast shading passes listed for the exact
 // pass - [0] surface, [1] sky - then per certificate site (ref_math.h
 // CertSite) the listed paths in which it failed (kRedoWords words).
-constexpr int kRedoWords = 2 + CS_COUNT;
 __device__ __forceinline__ void tally_redo(unsigned long long* tally, int kind, uint32_t fail_mask)
 {
     atomicAdd(tally + kind, 1ull);
@@ -279,7 +213,6 @@ constexpr int kWalkUnroll = 2;     // node steps per leaf phase (1 and 3 measure
 // PTG_WALK_BLOCKS[_ANY] override them (the results do not depend on them).
 constexpr uint32_t kWalkResident[2] = {4, 0};
 constexpr uint32_t kWalkBlocksPerCu[2] = {3, 3};
-constexpr uint32_t kWfSlots = 2;           // concurrent wavefront chunk pipelines (ptg_context::Slot)
 constexpr uint32_t kBands = 1024;   // XCD bands of a walk queue: a multiple of the XCD count (8 on MI355X)
 // a chunk's device counters: per round the queue / NEE list lengths (2 words,
 // plus 4 spare), the hit / sky list lengths (2), the redo list lengths (2)
@@ -779,10 +712,6 @@ __global__ __launch_bounds__(kBlock) void k_trace(DevScene sc, PixelMap pm, uint
     if(COUNT) flush_counters(cnt, counters, (p < pm.npix && jj < nj) ? 1u : 0u);
 }
 
-// Rec. 709 luminance of the moments and of the guided denoiser: three
-// products, two sums, each one float32 rounding
-__device__ __forceinline__ float lum709(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
 // The fold's arithmetic, each operation one float32 rounding (k_accumulate,
 // k_ad_fold, k_ad_resolve, tp_blend and ad_noisy share it).
 //
@@ -808,20 +737,6 @@ __device__ __forceinline__ void fold_samples(const float4* samples, uint32_t npi
                 ++n;
             }
     }
-}
-// the variance of the mean of n samples with the moments (m1, m2); a NaN gives 0
-__device__ __forceinline__ float var_of_mean(float m1, float m2, float n)
-{
-    const float d = m2 - m1 * m1;
-    const float var = d > 0.0f ? d : 0.0f;
-    return n >= 2.0f ? var / (n - 1.0f) : 0.0f;
-}
-// the sums (s1, s2) of n > 0 finite samples -> (m1, m2, variance of the mean, n)
-__device__ __forceinline__ float4 moments_of(float s1, float s2, uint32_t n)
-{
-    const float nf = (float)n;
-    const float m1 = s1 / nf, m2 = s2 / nf;
-    return make_float4(m1, m2, var_of_mean(m1, m2, nf), nf);
 }
 
 // acc[p] (+)= samples in index order; on the last chunk / spp and tonemap.
@@ -941,12 +856,6 @@ __global__ __launch_bounds__(kBlock) void k_rays(DevScene sc, uint32_t tlas_root
     w[7] = shadow ? 1u : 0u;
 }
 
-__global__ void k_tonemap(uint32_t n, const float4* __restrict__ in, uchar4* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = tonemap(V3(in[i].x, in[i].y, in[i].z));
-}
-
 __global__ void k_scatter_tiles(PixelMap pm, const uchar4* __restrict__ tiles, uchar4* __restrict__ image)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -955,7 +864,7 @@ __global__ void k_scatter_tiles(PixelMap pm, const uchar4* __restrict__ tiles, u
     if(pm.pixel(p, x, y)) image[size_t(y) * pm.img_w + x] = tiles[p];
 }
 
-// ---- first-hit feature buffers and the a-trous denoiser ----
+// ---- first-hit feature buffers (the a-trous denoiser over them: image_ops.hip) ----
 
 // The first ray path_trace_pixel traces for (pixel, sample): camera_ray's
 // origin and direction with tmin 0 and tmax MAX_RAY_DIST, and the subframe.
@@ -1056,386 +965,6 @@ __global__ __launch_bounds__(kBlock) void k_features(DevScene sc, PixelMap pm, u
             out_normal_depth[p] = make_float4(acc[4] / spp, acc[5] / spp, acc[6] / spp, acc[7] / spp);
         }
     }
-}
-
-// max(albedo, floor) of the denoiser's (de)modulation; a NaN albedo stays NaN
-__device__ __forceinline__ float dn_floor(float a, float fl) { return (a > fl || a != a) ? a : fl; }
-
-// a variance the guided denoiser may use: >= 0 and finite, else 0
-__device__ __forceinline__ float dn_var_ok(float v) { return (v >= 0.0f && __builtin_isfinite(v)) ? v : 0.0f; }
-
-// I0 = radiance / max(albedo, floor) per channel.  GUIDED (ptg_denoise_guided):
-// the w lane is V0, the variance of the pixel's mean luminance (moments.z) /
-// lum(max(albedo, floor))^2; else it is 0 and moments is not read.
-template<bool GUIDED>
-__global__ __launch_bounds__(kBlock) void k_dn_demodulate(uint32_t n, float fl, const float4* __restrict__ radiance,
-                                                          const float4* __restrict__ albedo,
-                                                          const float4* __restrict__ moments, float4* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n) return;
-    const float4 r = radiance[i], a = albedo[i];
-    const float mx = dn_floor(a.x, fl), my = dn_floor(a.y, fl), mz = dn_floor(a.z, fl);
-    float4 o = make_float4(r.x / mx, r.y / my, r.z / mz, 0.0f);
-    if constexpr(GUIDED)
-    {
-        const float v = dn_var_ok(moments[i].z);
-        const float ml = lum709(mx, my, mz);
-        o.w = dn_var_ok(v / (ml * ml));
-    }
-    out[i] = o;
-}
-
-// One iteration's arguments: the fixed filter's colour range (ptg_denoise) or
-// the guided filter's luminance range (ptg_denoise_guided), and what they share
-struct DenoiseStep {
-    static constexpr bool guided = false;
-    uint32_t w, h, step;
-    float var_color, var_albedo, var_normal, var_depth;   // sigma * sigma of this iteration
-};
-struct DenoiseGuidedStep {
-    static constexpr bool guided = true;
-    uint32_t w, h, step;
-    float sigma_luminance, variance_floor;
-    float var_albedo, var_normal, var_depth;              // sigma * sigma
-};
-
-// One edge-avoiding a-trous iteration, one work-item per pixel: 5 x 5 taps
-// `step` pixels apart, dy outer and dx inner, every operation one float32
-// rounding in the order DESIGN.md gives; the weight's exp is glibc's.
-// The fixed filter (STEP = DenoiseStep) compares colours against var_color.
-// The guided one (DenoiseGuidedStep) filters (I.xyz, V): a 3 x 3 prefilter of
-// V at distance 1 sets the range of the luminance difference, and the taps
-// filter V with the squares of the weights.
-template<class STEP>
-__global__ __launch_bounds__(kBlock) void k_dn_atrous(STEP a, const float4* __restrict__ I,
-                                                      const float4* __restrict__ albedo,
-                                                      const float4* __restrict__ normal_depth, float4* __restrict__ out)
-{
-    constexpr bool GUIDED = STEP::guided;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= a.w * a.h) return;
-    const int32_t x = (int32_t)(i % a.w), y = (int32_t)(i / a.w);
-    const float4 Ip = I[i], Ap = albedo[i], Np = normal_depth[i];
-    float den = 0.0f, lp = 0.0f;
-    if constexpr(GUIDED)
-    {
-        float gs = 0.0f, gn = 0.0f;
-        for(int32_t dy = -1; dy <= 1; ++dy)
-        {
-            const int32_t qy = y + dy;
-            if(qy < 0 || qy >= (int32_t)a.h) continue;
-            const float ty = dy == 0 ? 0.5f : 0.25f;
-            for(int32_t dx = -1; dx <= 1; ++dx)
-            {
-                const int32_t qx = x + dx;
-                if(qx < 0 || qx >= (int32_t)a.w) continue;
-                const float tx = dx == 0 ? 0.5f : 0.25f;
-                const float4 Iq = I[size_t(qy) * a.w + size_t(qx)];
-                if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
-                const float gw = ty * tx;
-                gs = gs + gw * Iq.w;
-                gn = gn + gw;
-            }
-        }
-        const float g = gn > 0.0f ? gs / gn : 0.0f;
-        den = a.sigma_luminance * sqrtf(g) + a.variance_floor;
-        lp = lum709(Ip.x, Ip.y, Ip.z);
-    }
-    const bool p_finite = finite3(V3(Ip.x, Ip.y, Ip.z));
-    const float zp2 = Np.w * Np.w;
-    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
-    for(int32_t dy = -2; dy <= 2; ++dy)
-    {
-        const int64_t qy = (int64_t)y + (int64_t)dy * a.step;
-        if(qy < 0 || qy >= (int64_t)a.h) continue;
-        const float hy = dy == 0 ? 0.375f : (dy == -1 || dy == 1) ? 0.25f : 0.0625f;
-        for(int32_t dx = -2; dx <= 2; ++dx)
-        {
-            const int64_t qx = (int64_t)x + (int64_t)dx * a.step;
-            if(qx < 0 || qx >= (int64_t)a.w) continue;
-            const float hx = dx == 0 ? 0.375f : (dx == -1 || dx == 1) ? 0.25f : 0.0625f;
-            const size_t q = size_t(qy) * a.w + size_t(qx);
-            const float4 Iq = I[q];
-            if(!finite3(V3(Iq.x, Iq.y, Iq.z))) continue;
-            const float4 Aq = albedo[q], Nq = normal_depth[q];
-            float ec = 0.0f;                                            // the colour or luminance term
-            if constexpr(GUIDED)
-                ec = p_finite ? fabsf(lp - lum709(Iq.x, Iq.y, Iq.z)) / den : 0.0f;
-            else
-            {
-                float dc = 0.0f;
-                if(p_finite)
-                {
-                    const float cx = Ip.x - Iq.x, cy = Ip.y - Iq.y, cz = Ip.z - Iq.z;
-                    dc = (cx * cx + cy * cy) + cz * cz;
-                }
-                ec = dc / a.var_color;
-            }
-            const float ax = Ap.x - Aq.x, ay = Ap.y - Aq.y, az = Ap.z - Aq.z, aw = Ap.w - Aq.w;
-            const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
-            const float nx = Np.x - Nq.x, ny = Np.y - Nq.y, nz = Np.z - Nq.z;
-            const float dn = (nx * nx + ny * ny) + nz * nz;
-            const float dz = Np.w - Nq.w;
-            const float zq2 = Nq.w * Nq.w;
-            const float zmax = (zp2 > zq2 || zp2 != zp2) ? zp2 : zq2;   // a NaN depth stays NaN
-            const float dz2 = (dz * dz) / (zmax + 1e-12f);
-            const float e = ((ec + da / a.var_albedo) + dn / a.var_normal) + dz2 / a.var_depth;
-            if(!__builtin_isfinite(e)) continue;
-            const float wgt = (hy * hx) * (float)dexp(-(double)e);
-            sw = sw + wgt;
-            sx = sx + wgt * Iq.x;
-            sy = sy + wgt * Iq.y;
-            sz = sz + wgt * Iq.z;
-            if constexpr(GUIDED) sv = sv + (wgt * wgt) * Iq.w;
-        }
-    }
-    // the w lane: the guided filter's variance, else 0
-    out[i] = sw > 0.0f ? make_float4(sx / sw, sy / sw, sz / sw, GUIDED ? dn_var_ok(sv / (sw * sw)) : 0.0f)
-                       : make_float4(Ip.x, Ip.y, Ip.z, GUIDED ? dn_var_ok(Ip.w) : 0.0f);
-}
-
-// out = I * max(albedo, floor), w = 0; optionally its tonemap
-__global__ __launch_bounds__(kBlock) void k_dn_remodulate(uint32_t n, float fl, const float4* __restrict__ I,
-                                                          const float4* __restrict__ albedo, float4* __restrict__ out,
-                                                          uchar4* __restrict__ out_bgra)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n) return;
-    const float4 v = I[i], a = albedo[i];
-    const f3 c = V3(v.x * dn_floor(a.x, fl), v.y * dn_floor(a.y, fl), v.z * dn_floor(a.z, fl));
-    out[i] = make_float4(c.x, c.y, c.z, 0.0f);
-    if(out_bgra) out_bgra[i] = tonemap(c);
-}
-
-// ---- temporal accumulation (several cameras and the history clamp: 4.17) ----
-
-// The parts of a ptg_camera the reprojection reads.
-struct TemporalCam {
-    m3 ori;
-    f3 pos;
-    float aspect, ifl, fd;
-};
-constexpr uint32_t kTemporalMaxCams = 512;  // ptg_temporal_accumulate_clamped's n_cams
-// k_temporal_accumulate's arguments.  The plain entry reads `cam` and none of
-// the clamped entry's fields; the clamped entry reads those and not `cam`.
-struct TemporalArgs {
-    uint32_t w, h;
-    uint32_t has_history;                  // 0: first frame, the hist_* pointers are null
-    float max_history, depth_tolerance, normal_tolerance, albedo_tolerance;
-    TemporalCam cam, hist;                 // plain: this frame's camera; the history's
-    uint32_t n_cams;                       // clamped: this frame's cameras, in the context's buffer
-    uint32_t clamp_radius;                 // clamped: 0: no clamp
-    float clamp_sigma, clipped_history;    // clamped
-};
-
-// Steps 2-4 of the definition for one camera: the first-hit point of pixel
-// (x, y), from its centre ray through `cam` and the mean depth z, is
-// projected into `hist`; the four bilinear taps around it that show the same
-// surface (depth, normal, albedo) add into the seven running sums.  A camera
-// that fails a test adds nothing.
-struct TemporalSums {
-    float sw = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
-};
-__device__ __forceinline__ void tp_gather(TemporalSums& s, uint32_t w, uint32_t h, float depth_tolerance,
-                                          float normal_tolerance, float albedo_tolerance, const TemporalCam& cam,
-                                          const TemporalCam& hist, uint32_t x, uint32_t y, float z, const float4& A,
-                                          const float4& G, const float4* __restrict__ hist_radiance,
-                                          const float4* __restrict__ hist_moments, const float4* __restrict__ hist_albedo,
-                                          const float4* __restrict__ hist_normal_depth)
-{
-    const float uvx = (((float)x + 0.5f) / (float)w * 2.0f - 1.0f) * cam.aspect;
-    const float uvy = -(((float)y + 0.5f) / (float)h * 2.0f - 1.0f);
-    const f3 d = normalize(V3(uvx * cam.ifl * cam.fd, uvy * cam.ifl * cam.fd, -1.0f * cam.fd));
-    const f3 dir = mul_m3v3(cam.ori, d);
-    const f3 P = cam.pos + dir * z;
-    const f3 q = P - hist.pos;
-    const f3 l = mul_v3m3(q, hist.ori);
-    if(l.z < 0.0f)
-    {
-        const float t = -l.z;
-        const float sx = (l.x / t) / hist.ifl / hist.aspect;
-        const float sy = -((l.y / t) / hist.ifl);
-        const float fx = (sx + 1.0f) * 0.5f * (float)w - 0.5f;
-        const float fy = (sy + 1.0f) * 0.5f * (float)h - 0.5f;
-        const float ze = fsqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
-        if(__builtin_isfinite(fx) && __builtin_isfinite(fy))
-        {
-            const float ix = floorf(fx), iy = floorf(fy);
-            const float tx = fx - ix, ty = fy - iy;
-            const float xmax = (float)(w - 1u), ymax = (float)(h - 1u);
-#pragma unroll
-            for(int b = 0; b < 2; ++b)
-            {
-                const float Y = iy + (float)b;
-                const float wy = b ? ty : 1.0f - ty;
-#pragma unroll
-                for(int c = 0; c < 2; ++c)
-                {
-                    const float X = ix + (float)c;
-                    const float bw = (c ? tx : 1.0f - tx) * wy;
-                    // inside on the floats; an integer only after that
-                    if(!(X >= 0.0f && X <= xmax && Y >= 0.0f && Y <= ymax)) continue;
-                    const size_t t4 = size_t((uint32_t)Y) * w + size_t((uint32_t)X);
-                    const float4 HA = hist_albedo[t4];
-                    if(!(HA.w > 0.0f)) continue;
-                    const float4 H = hist_radiance[t4];
-                    if(!finite3(V3(H.x, H.y, H.z))) continue;
-                    const float4 HM = hist_moments[t4];
-                    if(!(HM.w > 0.0f)) continue;
-                    const float4 HG = hist_normal_depth[t4];
-                    const float zh = HG.w / HA.w;
-                    const float zm = zh > ze ? zh : ze;
-                    if(!(fabsf(zh - ze) <= depth_tolerance * zm)) continue;
-                    const float nx = G.x - HG.x, ny = G.y - HG.y, nz = G.z - HG.z;
-                    const float dn = (nx * nx + ny * ny) + nz * nz;
-                    if(!(dn <= normal_tolerance)) continue;
-                    const float ax = A.x - HA.x, ay = A.y - HA.y, az = A.z - HA.z, aw = A.w - HA.w;
-                    const float da = ((ax * ax + ay * ay) + az * az) + aw * aw;
-                    if(!(da <= albedo_tolerance)) continue;
-                    s.sw = s.sw + bw;
-                    s.cx = s.cx + bw * H.x;
-                    s.cy = s.cy + bw * H.y;
-                    s.cz = s.cz + bw * H.z;
-                    s.s1 = s.s1 + bw * HM.x;
-                    s.s2 = s.s2 + bw * HM.y;
-                    s.sn = s.sn + bw * HM.w;
-                }
-            }
-        }
-    }
-}
-
-// Steps 6-7: the history (hx, hy, hz; h1, h2; hn samples, not yet capped at
-// max_history) blended with this frame's R and M by their sample counts, or
-// the history alone where this frame brings nothing usable.
-__device__ __forceinline__ void tp_blend(float hx, float hy, float hz, float h1, float h2, float hn, float max_history,
-                                         const float4& R, const float4& M, float4& oc, float4& om)
-{
-    const float nh = hn < max_history ? hn : max_history;
-    if(finite3(V3(R.x, R.y, R.z)) && M.w > 0.0f)
-    {
-        const float nt = nh + M.w;
-        const float al = M.w / nt;
-        oc = make_float4(hx + al * (R.x - hx), hy + al * (R.y - hy), hz + al * (R.z - hz), 0.0f);
-        const float m1 = h1 + al * (M.x - h1), m2 = h2 + al * (M.y - h2);
-        om = make_float4(m1, m2, var_of_mean(m1, m2, nt), nt);
-    }
-    else
-    {   // nothing usable in this frame: the history alone
-        oc = make_float4(hx, hy, hz, 0.0f);
-        om = make_float4(h1, h2, var_of_mean(h1, h2, nh), nh);
-    }
-}
-
-// One work-item per pixel: the pixel's first-hit point, from its centre ray
-// through this frame's camera and its mean depth, is projected into `hist`;
-// the four bilinear taps around it that show the same surface (depth, normal,
-// albedo) give the history's radiance and moments, which are blended with this
-// frame's by their sample counts.  Every operation is one float32 rounding in
-// the order DESIGN.md gives.  This frame's images are read at the pixel alone
-// (the outputs may be the radiance and moments themselves: no __restrict__
-// on those four); the history is gathered.
-//
-// The plain entry (CLAMPED = false) has one camera, a.cam in the kernel
-// arguments; `cams` and `flags` are null and never read.  The clamped entry
-// has two insertions.  The reprojection runs once per camera of `cams` (a
-// wave-uniform loop: the cameras come through scalar loads) into the same
-// seven sums, so the history of a motion-blurred pixel is gathered along the
-// blur.  With clamp_radius r > 0 the history's colour is then clamped, per
-// channel, to mean +- clamp_sigma standard deviations of the finite pixels of
-// this frame's (2r + 1)^2 window; a clipped history's first moment follows the
-// colour, its second keeps the variance, and its sample count is capped at
-// clipped_history.  `radiance` is gathered by the clamp: with r > 0 it is not
-// out_radiance (the host refuses that).  flags (optional): bit 0 the pixel
-// found history, bit 1 its history was clipped.
-template<bool CLAMPED>
-__global__ __launch_bounds__(kBlock) void k_temporal_accumulate(
-    TemporalArgs a, const float4* radiance, const float4* moments, const float4* __restrict__ albedo,
-    const float4* __restrict__ normal_depth, const float4* __restrict__ hist_radiance,
-    const float4* __restrict__ hist_moments, const float4* __restrict__ hist_albedo,
-    const float4* __restrict__ hist_normal_depth, float4* out_radiance, float4* out_moments, uchar4* __restrict__ out_bgra,
-    const TemporalCam* __restrict__ cams, uint8_t* __restrict__ flags)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= a.w * a.h) return;
-    const uint32_t x = i % a.w, y = i / a.w;
-    const float4 R = radiance[i], M = moments[i], A = albedo[i], G = normal_depth[i];
-    TemporalSums s;
-    const float cov = A.w;
-    if(a.has_history && cov > 0.0f)
-    {
-        const float z = G.w / cov;
-        auto gather = [&](const TemporalCam& cam) {
-            tp_gather(s, a.w, a.h, a.depth_tolerance, a.normal_tolerance, a.albedo_tolerance, cam, a.hist, x, y, z, A, G,
-                      hist_radiance, hist_moments, hist_albedo, hist_normal_depth);
-        };
-        if constexpr(CLAMPED)
-            for(uint32_t k = 0; k < a.n_cams; ++k) gather(cams[k]);
-        else
-            gather(a.cam);   // not a one-trip loop: that compiles to 2 VGPRs more
-    }
-    float4 oc = make_float4(R.x, R.y, R.z, 0.0f), om = M;      // no history: this frame's bits
-    uint32_t fl = 0;
-    if(s.sw > 0.0f)
-    {
-        fl = 1u;
-        float hc[3] = {s.cx / s.sw, s.cy / s.sw, s.cz / s.sw};
-        float h1 = s.s1 / s.sw, h2 = s.s2 / s.sw, hn = s.sn / s.sw;
-        if(CLAMPED && a.clamp_radius)
-        {
-            const int32_t r = (int32_t)a.clamp_radius;
-            int32_t n = 0;
-            float su[3] = {0.0f, 0.0f, 0.0f}, sq[3] = {0.0f, 0.0f, 0.0f};
-            for(int32_t dy = -r; dy <= r; ++dy)
-            {
-                const int32_t qy = (int32_t)y + dy;
-                if(qy < 0 || qy >= (int32_t)a.h) continue;
-                for(int32_t dx = -r; dx <= r; ++dx)
-                {
-                    const int32_t qx = (int32_t)x + dx;
-                    if(qx < 0 || qx >= (int32_t)a.w) continue;
-                    const float4 Rq = radiance[size_t(qy) * a.w + size_t(qx)];
-                    if(!finite3(V3(Rq.x, Rq.y, Rq.z))) continue;
-                    ++n;
-                    su[0] = su[0] + Rq.x; sq[0] = sq[0] + Rq.x * Rq.x;
-                    su[1] = su[1] + Rq.y; sq[1] = sq[1] + Rq.y * Rq.y;
-                    su[2] = su[2] + Rq.z; sq[2] = sq[2] + Rq.z * Rq.z;
-                }
-            }
-            if(n > 0)
-            {
-                const float nf = (float)n;
-                const float l0 = lum709(hc[0], hc[1], hc[2]);
-                bool clipped = false;
-#pragma unroll
-                for(int c = 0; c < 3; ++c)
-                {
-                    const float mu = su[c] / nf, e2 = sq[c] / nf;
-                    const float d = e2 - mu * mu;
-                    const float rr = a.clamp_sigma * fsqrt(d > 0.0f ? d : 0.0f);
-                    const float lo = mu - rr, hi = mu + rr;
-                    // a NaN bound compares false: the value stays
-                    if(hc[c] < lo) { hc[c] = lo; clipped = true; }
-                    else if(hc[c] > hi) { hc[c] = hi; clipped = true; }
-                }
-                if(clipped)
-                {
-                    fl = 3u;
-                    const float dl = lum709(hc[0], hc[1], hc[2]) - l0;
-                    const float g1 = h1 + dl;
-                    h2 = h2 + (g1 * g1 - h1 * h1);
-                    h1 = g1;
-                    hn = hn < a.clipped_history ? hn : a.clipped_history;
-                }
-            }
-        }
-        tp_blend(hc[0], hc[1], hc[2], h1, h2, hn, a.max_history, R, M, oc, om);
-    }
-    out_radiance[i] = oc;
-    out_moments[i] = om;
-    if(out_bgra) out_bgra[i] = tonemap(V3(oc.x, oc.y, oc.z));
-    if(CLAMPED && flags) flags[i] = (uint8_t)fl;
 }
 
 // ---- adaptive sampling ----
@@ -1573,228 +1102,7 @@ __global__ __launch_bounds__(kBlock) void k_ad_resolve(uint32_t npix, const floa
     if(out_samples) out_samples[p] = ns;
 }
 
-// ---------------------------------------------------------------- runtime --
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { if(p) (void)hipFree(p); }
-    hipError_t reserve(size_t n)
-    {
-        if(n <= bytes && p) return hipSuccess;
-        if(p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        if(n == 0) return hipSuccess;
-        hipError_t e = hipMalloc(&p, n);
-        if(e == hipSuccess) bytes = n;
-        return e;
-    }
-    template<typename T> T* as() const { return static_cast<T*>(p); }
-};
-
-// Pinned host staging for asynchronous uploads; `done` marks the end of the
-// copies that last read it.
-struct HostStage {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-    ~HostStage()
-    {
-        if(done)
-        {
-            (void)hipEventSynchronize(done);
-            (void)hipEventDestroy(done);
-        }
-        if(p) (void)hipHostFree(p);
-    }
-    // waits for the copies that last read it, then grows it to n bytes
-    hipError_t reserve(size_t n)
-    {
-        if(!done)
-            if(hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming)) return e;
-        if(hipError_t e = hipEventSynchronize(done)) return e;
-        if(n <= bytes && p) return hipSuccess;
-        if(p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
-        hipError_t e = hipHostMalloc(&p, std::max<size_t>(n, 1), hipHostMallocDefault);
-        if(e == hipSuccess) bytes = std::max<size_t>(n, 1);
-        return e;
-    }
-};
-
-int hip_fail(hipError_t e, const char* what)
-{
-    set_last_error(std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
-    return PTG_E_HIP;
-}
-
-#define PTG_HIP(call)                                                        \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if(e_ != hipSuccess) return hip_fail(e_, #call);                     \
-    } while(0)
-
-int fail(int code, const std::string& msg)
-{
-    set_last_error(msg);
-    return code;
-}
-
-uint32_t grid_for(size_t n, uint32_t block = kBlock) { return uint32_t((n + block - 1) / block); }
-
-} // namespace
-
-struct ptg_context {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool counting = false;
-    // static scene: the shading arrays in reference layout and the triangle
-    // records
-    DevBuf indices, pos, normal, albedo, material, tris, tri_shade;
-    // the host's copy of the scene and everything packed from it so far
-    // (host/block_bvh.h; the BLAS blocks' device copy leads `blocks`)
-    BlockCache cache;
-    size_t blas_on_device = 0;                           // leading cache.blas entries already in `blocks`
-    bool scene_ready = false;
-    // frame: blocks = [BLAS blocks][this frame's TLAS blocks]
-    DevBuf blocks, tlas_root, subframes, inst_trav, inst_shade, inst_box, jobs, polygon, spill;
-    HostStage stage[2];                                  // ptg_upload_frame's pinned staging, used alternately
-    uint32_t stage_next = 0;
-    size_t block_count = 0, subframe_count = 0, instance_count = 0;
-    uint32_t stack_bound = 0;                            // TLAS + BLAS stack bound of this frame (entries)
-    std::vector<uint32_t> host_tlas_root;
-    bool frame_ready = false;
-    // render workspace
-    DevBuf acc, tmp_a, tmp_b, tmp_c, counters;
-    DevBuf mom;                            // ptg_render_moments: the running (s1, s2, n) per pixel, beside acc
-    DevBuf feat_acc;                       // ptg_render_with_features: the eight running feature sums per pixel (k_fold_features)
-    DevBuf dn_a, dn_b;                     // ptg_denoise: the demodulated image and its ping-pong partner
-    DevBuf feat_spill;                     // ptg_render_features: the walk stacks' spill areas
-    DevBuf ad_list, ad_count;              // ptg_render_adaptive: the active pixels' ids and their number
-    DevBuf tp_cams;                        // ptg_temporal_accumulate_clamped: the call's cameras (kTemporalMaxCams TemporalCam)
-    HostStage tp_stage[2];                 // their pinned staging, used alternately
-    uint32_t tp_stage_next = 0;
-    uint32_t ad_passes_run = 0;            // ptg_last_adaptive_stats
-    uint64_t ad_active[16] = {};
-    DevBuf debug;                          // PTG_DEBUG builds: kDebugSlots violation counters
-    uint64_t last_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // k_trace launch timing (HIP events on the launch stream)
-    bool timing = false;
-    std::vector<hipEvent_t> ev_start, ev_stop;
-    std::vector<int> ev_kind;
-    size_t ev_used = 0;
-    // 0: wavefront pipeline (default), 1: megakernel
-    int pipeline = 0;
-    uint32_t persistent_blocks = 2048;
-    uint32_t walk_grid[2] = {2048, 2048};
-    uint32_t walk_xcds[2] = {1, 1};        // XCDs the walk grid is dealt over (8 when the grid divides evenly)
-    uint32_t walk_lds[2] = {0, 0};         // dynamic LDS per walk block: cold state + stack rings, padded to cap residency
-    uint32_t hbm_pct = 35;                 // wavefront state: at most this share of HBM per chunk pipeline (ptg_set_hbm_share)
-    // wavefront: <= 2^chunk_log2 live paths per chunk.  2^27 paths x 380 B
-    // (kStateBytesPerPath 364 + the 16 B sample) = 51 GB per pipeline, ~35% of an MI355X's HBM for the two pipelines
-    // together, so a default render leaves most of the GPU to other tenants;
-    // 2^28 (~71%) is 1-3% faster on a GPU the renderer owns alone.
-    uint32_t chunk_log2 = 27;
-    uint64_t kind_counters[6][8] = {};
-    uint64_t walk_stats[2][8] = {};        // counting builds: WalkStat tallies of the closest-hit / any-hit walks
-    uint64_t redo_stats[kRedoWords] = {};  // counting builds: the certified shading's redo tallies (tally_redo)
-    // Wavefront chunk pipelines ("slots").  With two slots, consecutive
-    // chunks run concurrently on their own stream pairs and buffers, so one
-    // chunk's round-0 walk and shade overlap the other's sky and shadow
-    // kernels; k_accumulate still folds the chunks in sample order, each on
-    // its chunk's slot stream, chained by events across the slots (fold_chunk).
-    // The megakernel and concurrency levels 0 / 1 use slot 0 alone.
-    struct Slot {
-        // main: the slot's first camera, closest-hit walk, classify, shade,
-        // fold; side: shadow walk, sky and the camera of the slot's next chunk
-        // (trace_chunk_wavefront).  Slot 0 has no main stream of its own: its
-        // chunks run on the caller's stream (main_of)
-        hipStream_t main = nullptr, side = nullptr;
-        // the events that order main and side; ev_acc: the slot's last fold done
-        hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_acc = nullptr;
-        DevBuf state, samples;   // path state (SlotState), the chunk's per-sample results
-        DevBuf feat;             // a fused render's per-sample features: two arrays laid out like `samples`
-    };
-    Slot slot[kWfSlots];
-    hipStream_t main_of(uint32_t k) const { return k ? slot[k].main : stream; }
-    uint32_t concurrency = 2;              // ptg_set_concurrency
-    hipEvent_t ev_render_start = nullptr;
-    hipEvent_t ev_first_camera = nullptr;  // a render's first camera kernels take turns (trace_chunk_wavefront)
-    ~ptg_context()
-    {
-        for(Slot& b: slot)
-        {
-            for(hipEvent_t e: {b.ev_main, b.ev_side, b.ev_acc})
-                if(e) (void)hipEventDestroy(e);
-            for(hipStream_t st: {b.main, b.side})
-                if(st) (void)hipStreamDestroy(st);
-        }
-        if(ev_render_start) (void)hipEventDestroy(ev_render_start);
-        if(ev_first_camera) (void)hipEventDestroy(ev_first_camera);
-        for(hipEvent_t e: ev_start) (void)hipEventDestroy(e);
-        for(hipEvent_t e: ev_stop) (void)hipEventDestroy(e);
-    }
-
-    // Wait for everything queued on the context's streams: the caller's
-    // stream and every slot's own.
-    hipError_t drain() const
-    {
-        for(uint32_t k = 0; k < kWfSlots; ++k)
-            for(hipStream_t st: {main_of(k), slot[k].side})
-                if(hipError_t e = hipStreamSynchronize(st)) return e;
-        return hipSuccess;
-    }
-    // Grow a workspace buffer.  Growing frees the old allocation, which work
-    // still queued on the context's streams may read: drain them first (rare,
-    // the buffers only grow), rather than rely on hipFree's implicit sync.
-    hipError_t grow(DevBuf& b, size_t n) const
-    {
-        if(n <= b.bytes && b.p) return hipSuccess;
-        if(b.p)
-            if(hipError_t e = drain()) return e;
-        return b.reserve(n);
-    }
-
-    DevScene scene_args(const ptg_render_config* cfg) const
-    {
-        DevScene s;
-        s.blocks = blocks.as<BlockCopy>();
-        s.tlas_root = tlas_root.as<uint32_t>();
-        s.tris = tris.as<TriRec>();
-        s.tri_shade = tri_shade.as<TriShade>();
-        s.inst_trav = inst_trav.as<InstTrav>();
-        s.inst_shade = inst_shade.as<InstShade>();
-        s.inst_box = inst_box.as<InstBox>();
-        s.indices = indices.as<uint32_t>();
-        s.normal = normal.as<float>();
-        s.albedo = albedo.as<float>();
-        s.material = material.as<float>();
-        s.subframes = subframes.as<uint8_t>();
-        s.polygon = polygon.as<float2>();
-        s.width = cfg ? cfg->width : 0;
-        s.height = cfg ? cfg->height : 0;
-        s.spp = cfg ? cfg->samples_per_pixel : 0;
-        s.max_bounces = cfg ? cfg->max_bounces : 0;
-        s.student_id = cfg ? cfg->student_id : 0;
-        s.blur_step = cfg ? cfg->samples_per_motion_blur_step : 8;
-        s.subframe_count = uint32_t(subframe_count);
-        s.block_count = uint32_t(block_count);
-        s.spill = nullptr;
-        s.spill_stride = stack_bound;
-        s.tri_count = uint32_t(cache.indices.size() / 3);
-        s.inst_count = uint32_t(instance_count);
-        s.debug = PTG_DEBUG ? debug.as<uint32_t>() : nullptr;
-        s.attrs_finite = cache.attrs_finite ? 1u : 0u;
-        return s;
-    }
-};
-
-namespace {
-
-int bind(ptg_context* ctx)
-{
-    if(!ctx) return fail(PTG_E_INVALID, "null context");
-    PTG_HIP(hipSetDevice(ctx->device));
-    return PTG_OK;
-}
+// ---------------------------------------------------------- render driver --
 
 int check_cfg(const ptg_context* ctx, const ptg_render_config* cfg, uint32_t sample_end)
 {
@@ -1868,17 +1176,6 @@ int launch(ptg_context* ctx, int kind, hipStream_t st, dim3 grid, uint32_t lds, 
     launch_counted(ctx, st, grid, lds, counting, plain, args...);
     PTG_HIP(hipGetLastError());
     return timed_end(ctx, st);
-}
-
-// A launch of the other entry points, on ctx->stream, its launch error
-// checked: neither timed nor counted (ptg_last_kernel_times lists the render
-// path alone).  `blocks` of kBlock work-items: grid_for(n) for one per element.
-template<typename... P, typename... A>
-int launch_plain(ptg_context* ctx, uint32_t blocks, void (*kernel)(P...), const A&... args)
-{
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, args...);
-    PTG_HIP(hipGetLastError());
-    return PTG_OK;
 }
 
 // A render call's fixed parts, shared by the steps render_map and
@@ -2430,46 +1727,6 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
     return end_render(ctx);
 }
 
-// What ptg_denoise and ptg_denoise_guided do once their parameters are
-// checked: demodulate into dn_a, `iterations` a-trous passes between dn_a and
-// dn_b with the step record step_of(k) (a DenoiseStep or a DenoiseGuidedStep,
-// which selects the kernels), remodulate into out_radiance.  `moments` is read
-// by the guided demodulate alone.
-template<class F>
-int denoise_passes(ptg_context* ctx, uint32_t w, uint32_t h, uint32_t iterations, float albedo_floor, F step_of,
-                   const ptg_float4* radiance, const ptg_float4* albedo, const ptg_float4* normal_depth,
-                   const ptg_float4* moments, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
-{
-    using Step = decltype(step_of(0u));
-    if(uint64_t(w) * h == 0) return PTG_OK;
-    if(uint64_t(w) * h >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
-    const uint32_t n = w * h;
-    const float4* rad = reinterpret_cast<const float4*>(radiance);
-    const float4* alb = reinterpret_cast<const float4*>(albedo);
-    float4* out = reinterpret_cast<float4*>(out_radiance);
-    uchar4* bgra = reinterpret_cast<uchar4*>(out_bgra);
-    if(iterations == 0)
-    {   // the input bits, unchanged
-        if(out != rad) PTG_HIP(hipMemcpyAsync(out, rad, size_t(n) * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-        return bgra ? launch_plain(ctx, grid_for(n), k_tonemap, n, out, bgra) : PTG_OK;
-    }
-    PTG_HIP(ctx->grow(ctx->dn_a, size_t(n) * sizeof(float4)));
-    PTG_HIP(ctx->grow(ctx->dn_b, size_t(n) * sizeof(float4)));
-    float4* cur = ctx->dn_a.as<float4>();
-    float4* nxt = ctx->dn_b.as<float4>();
-    if(int r = launch_plain(ctx, grid_for(n), k_dn_demodulate<Step::guided>, n, albedo_floor, rad, alb,
-                            reinterpret_cast<const float4*>(moments), cur))
-        return r;
-    for(uint32_t k = 0; k < iterations; ++k)
-    {
-        if(int r = launch_plain(ctx, grid_for(n), k_dn_atrous<Step>, step_of(k), cur, alb,
-                                reinterpret_cast<const float4*>(normal_depth), nxt))
-            return r;
-        std::swap(cur, nxt);
-    }
-    return launch_plain(ctx, grid_for(n), k_dn_remodulate, n, albedo_floor, cur, alb, out, bgra);
-}
-
 } // namespace
 
 extern "C" {
@@ -2594,189 +1851,6 @@ int ptg_context_set_stream(ptg_context* ctx, void* stream)
     }
     ctx->stream = next;
     return PTG_OK;
-}
-
-int ptg_upload_scene(ptg_context* ctx, const ptg_bvh_node* nodes, const ptg_bvh_link* links, size_t node_count,
-                     const uint32_t* indices, size_t index_count, const ptg_float3* pos, const ptg_float3* normal,
-                     const ptg_float4* albedo, const ptg_float4* material, size_t vertex_count)
-{
-    if(int r = bind(ctx)) return r;
-    if(!nodes || !links || !indices || !pos || !normal || !albedo || !material || node_count == 0 || index_count % 3)
-        return fail(PTG_E_INVALID, "ptg_upload_scene: bad arguments");
-    if(node_count >= (1u << 28) / 8 || index_count >= (1u << 31) || vertex_count >= (1u << 31))
-        return fail(PTG_E_RANGE, "ptg_upload_scene: scene too large for 32-bit indexing");
-    ctx->scene_ready = ctx->frame_ready = false;
-    ctx->blas_on_device = 0;
-    try
-    {
-        ctx->cache.set_scene(nodes, links, node_count, indices, index_count, pos, albedo, material, vertex_count);
-    }
-    catch(const std::bad_alloc&)
-    {
-        return fail(PTG_E_NOMEM, "ptg_upload_scene: host copy of the BVH nodes");
-    }
-    PTG_HIP(ctx->indices.reserve(index_count * 4));
-    PTG_HIP(ctx->pos.reserve(vertex_count * 16));
-    PTG_HIP(ctx->normal.reserve(vertex_count * 16));
-    PTG_HIP(ctx->albedo.reserve(vertex_count * 16));
-    PTG_HIP(ctx->material.reserve(vertex_count * 16));
-    // the walks address triangle records by 32-bit byte offsets (BlockWalker::leaf_select)
-    if(index_count / 3 * sizeof(TriRec) + 128 > 0xFFFFFFFFull)
-        return fail(PTG_E_RANGE, "triangle records above 4 GB (" + std::to_string(index_count / 3) + " triangles)");
-    // slack: the walk's leaf phase reads a triangle as four 16-byte rows (the
-    // 48-byte record and the next 16 bytes)
-    PTG_HIP(ctx->tris.reserve(std::max<size_t>(1, index_count / 3) * sizeof(TriRec) + 128));
-    PTG_HIP(ctx->tri_shade.reserve(std::max<size_t>(1, index_count / 3) * sizeof(TriShade)));
-    hipStream_t s = ctx->stream;
-    PTG_HIP(hipMemcpyAsync(ctx->indices.p, indices, index_count * 4, hipMemcpyHostToDevice, s));
-    PTG_HIP(hipMemcpyAsync(ctx->pos.p, pos, vertex_count * 16, hipMemcpyHostToDevice, s));
-    PTG_HIP(hipMemcpyAsync(ctx->normal.p, normal, vertex_count * 16, hipMemcpyHostToDevice, s));
-    PTG_HIP(hipMemcpyAsync(ctx->albedo.p, albedo, vertex_count * 16, hipMemcpyHostToDevice, s));
-    PTG_HIP(hipMemcpyAsync(ctx->material.p, material, vertex_count * 16, hipMemcpyHostToDevice, s));
-    PTG_HIP(hipStreamSynchronize(s));
-    ctx->scene_ready = true;
-    return PTG_OK;
-}
-
-namespace {
-
-// The body of ptg_upload_frame (which adds the C ABI's exception barrier).
-int upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subframe_count, const ptg_tlas_instance* instances,
-                 size_t instance_count, const ptg_bvh_node* frame_nodes, const ptg_bvh_link* frame_links, size_t first_node,
-                 size_t frame_node_count)
-{
-    ctx->frame_ready = false;
-    hipStream_t s = ctx->stream;
-
-    // Validate every handle, pack the BLASes no earlier frame named plus
-    // this frame's TLASes, and build the per-instance records and the mesh
-    // jobs (host/block_bvh.cpp, checked there before any kernel can follow a
-    // block link).  What this call packs joins the cache only at the commit
-    // below.
-    FramePack fp;
-    std::string err;
-    if(int r = ctx->cache.pack_frame(subframes, subframe_count, instances, instance_count, frame_nodes, frame_links,
-                                     first_node, frame_node_count, fp, err))
-        return fail(r, "ptg_upload_frame: " + err);
-    const std::vector<MeshJob>& mesh_jobs = fp.mesh_jobs;
-
-    // Device copies, asynchronous: everything the frame uploads is gathered
-    // into one of two pinned staging buffers and copied on the context's
-    // stream, behind the render already queued there - the host returns at
-    // once and the next render queues right behind the copies.  A staging
-    // buffer is reused only after its copies of two uploads ago completed.
-    // Growing a device buffer frees the old one, which an in-flight render
-    // may still read: the context's streams are drained first (rare).
-    auto grow = [&](DevBuf& b, size_t n) { return ctx->grow(b, n); };
-    // blocks = [BLAS blocks][TLAS blocks]; growing the buffer drops the BLAS
-    // blocks already there, which are then uploaded again
-    const std::vector<BlockCopy>& old_blas = ctx->cache.blas;
-    const size_t blas_total = old_blas.size() + fp.new_blas.size();
-    const size_t need = (blas_total + fp.tlas.size()) * sizeof(BlockCopy);
-    if(need > 0xFFFFFFFFull)   // the walks address blocks by 32-bit byte offsets (BlockWalker::block_rows)
-        return fail(PTG_E_RANGE, "block records above 4 GB (" + std::to_string(need) + " B)");
-    if(need > ctx->blocks.bytes)
-    {
-        PTG_HIP(grow(ctx->blocks, need + need / 8));
-        ctx->blas_on_device = 0;
-    }
-    PTG_HIP(grow(ctx->tlas_root, subframe_count * sizeof(uint32_t)));
-    PTG_HIP(grow(ctx->inst_trav, instance_count * sizeof(InstTrav)));
-    PTG_HIP(grow(ctx->inst_shade, instance_count * sizeof(InstShade)));
-    PTG_HIP(grow(ctx->inst_box, instance_count * sizeof(InstBox)));
-    PTG_HIP(grow(ctx->subframes, subframe_count * sizeof(ptg_subframe)));
-    PTG_HIP(grow(ctx->polygon, subframe_count * kPolyStride * sizeof(float2)));
-    if(!mesh_jobs.empty()) PTG_HIP(grow(ctx->jobs, mesh_jobs.size() * sizeof(MeshJob)));
-    BlockCopy* dev = ctx->blocks.as<BlockCopy>();
-    struct Part { const void* src; size_t n; void* dst; };
-    std::vector<Part> parts;
-    if(ctx->blas_on_device < old_blas.size())
-        parts.push_back({old_blas.data() + ctx->blas_on_device, (old_blas.size() - ctx->blas_on_device) * sizeof(BlockCopy),
-                         dev + ctx->blas_on_device});
-    parts.push_back({fp.new_blas.data(), fp.new_blas.size() * sizeof(BlockCopy), dev + old_blas.size()});
-    parts.push_back({fp.tlas.data(), fp.tlas.size() * sizeof(BlockCopy), dev + blas_total});
-    parts.push_back({fp.tlas_root.data(), subframe_count * sizeof(uint32_t), ctx->tlas_root.p});
-    parts.push_back({fp.inst_trav.data(), instance_count * sizeof(InstTrav), ctx->inst_trav.p});
-    parts.push_back({fp.inst_shade.data(), instance_count * sizeof(InstShade), ctx->inst_shade.p});
-    parts.push_back({fp.inst_box.data(), instance_count * sizeof(InstBox), ctx->inst_box.p});
-    parts.push_back({subframes, subframe_count * sizeof(ptg_subframe), ctx->subframes.p});
-    parts.push_back({mesh_jobs.data(), mesh_jobs.size() * sizeof(MeshJob), ctx->jobs.p});
-    size_t total = 0;
-    for(const Part& q: parts) total += (q.n + 255) & ~size_t(255);
-    HostStage& hs = ctx->stage[ctx->stage_next];
-    ctx->stage_next ^= 1u;
-    PTG_HIP(hs.reserve(total));
-    size_t off = 0;
-    for(const Part& q: parts)
-    {
-        if(q.n == 0) continue;
-        char* h = static_cast<char*>(hs.p) + off;
-        memcpy(h, q.src, q.n);
-        PTG_HIP(hipMemcpyAsync(q.dst, h, q.n, hipMemcpyHostToDevice, s));
-        off += (q.n + 255) & ~size_t(255);
-    }
-    PTG_HIP(hipEventRecord(hs.done, s));
-    hipLaunchKernelGGL(k_polygon_table, dim3(grid_for(subframe_count * kPolyStride)), dim3(kBlock), 0, s,
-                       ctx->subframes.as<uint8_t>(), uint32_t(subframe_count), ctx->polygon.as<float2>());
-    PTG_HIP(hipGetLastError());
-    if(!mesh_jobs.empty())
-    {
-        uint32_t maxt = 0;
-        for(const MeshJob& j: mesh_jobs) maxt = std::max(maxt, j.triangle_count);
-        dim3 grid(std::min<uint32_t>(grid_for(maxt), 4096), uint32_t(mesh_jobs.size()));
-        hipLaunchKernelGGL(k_pack_tris, grid, dim3(kBlock), 0, s, ctx->indices.as<uint32_t>(), ctx->pos.as<float4>(),
-                           ctx->tris.as<TriRec>(), ctx->jobs.as<MeshJob>(), ctx->normal.as<float4>(),
-                           ctx->albedo.as<float4>(), ctx->material.as<float4>(), ctx->tri_shade.as<TriShade>());
-        PTG_HIP(hipGetLastError());
-    }
-
-    // every upload is queued: what this call packed joins the cache
-    ctx->cache.commit(fp);
-    ctx->blas_on_device = ctx->cache.blas.size();
-    ctx->block_count = fp.total_blocks();
-    ctx->stack_bound = fp.stack_bound();
-    ctx->host_tlas_root = fp.tlas_root;
-    ctx->subframe_count = subframe_count;
-    ctx->instance_count = instance_count;
-    ctx->frame_ready = true;
-    return PTG_OK;
-}
-
-} // namespace
-
-int ptg_upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subframe_count,
-                     const ptg_tlas_instance* instances, size_t instance_count, const ptg_bvh_node* frame_nodes,
-                     const ptg_bvh_link* frame_links, size_t first_node, size_t frame_node_count)
-{
-    if(int r = bind(ctx)) return r;
-    if(!ctx->scene_ready) return fail(PTG_E_INVALID, "ptg_upload_frame: upload the scene first");
-    if(!subframes || !subframe_count || !instances || !instance_count || !frame_nodes || !frame_links || !frame_node_count)
-        return fail(PTG_E_INVALID, "ptg_upload_frame: bad arguments");
-    if(first_node != ctx->cache.nodes.size())
-        return fail(PTG_E_INVALID, "ptg_upload_frame: first_node must equal the uploaded static node count");
-    if(first_node + frame_node_count >= (1ull << 31)) return fail(PTG_E_RANGE, "ptg_upload_frame: too many nodes");
-    try
-    {
-        return upload_frame(ctx, subframes, subframe_count, instances, instance_count, frame_nodes, frame_links, first_node,
-                            frame_node_count);
-    }
-    catch(const std::bad_alloc&)
-    {
-        ctx->frame_ready = false;
-        return fail(PTG_E_NOMEM, "ptg_upload_frame: host memory");
-    }
-}
-
-int ptg_upload_from_scene(ptg_context* ctx, const ptg_scene* scene, int include_static)
-{
-    ptg_scene_view v;
-    if(int r = ptg_scene_view_get(scene, &v)) return r;
-    if(include_static)
-        if(int r = ptg_upload_scene(ctx, v.nodes, v.links, v.static_node_count, v.indices, v.index_count, v.pos, v.normal,
-                                    v.albedo, v.material, v.vertex_count))
-            return r;
-    return ptg_upload_frame(ctx, v.subframes, v.subframe_count, v.instances, v.instance_count, v.nodes + v.static_node_count,
-                            v.links + 8 * v.static_node_count, v.static_node_count, v.node_count - v.static_node_count);
 }
 
 static int rect_map(const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, PixelMap& pm)
@@ -2933,29 +2007,6 @@ int ptg_path_trace_samples(ptg_context* ctx, const ptg_render_config* cfg, size_
     return PTG_OK;
 }
 
-int ptg_tonemap_device(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_uchar4* out)
-{
-    if(int r = bind(ctx)) return r;
-    if(!n) return PTG_OK;
-    if(!color || !out || n >= (1u << 31)) return fail(PTG_E_INVALID, "ptg_tonemap_device: bad arguments");
-    return launch_plain(ctx, grid_for(n), k_tonemap, uint32_t(n), reinterpret_cast<const float4*>(color),
-                        reinterpret_cast<uchar4*>(out));
-}
-
-int ptg_tonemap(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_uchar4* out)
-{
-    if(int r = bind(ctx)) return r;
-    if(!n) return PTG_OK;
-    if(!color || !out || n >= (1u << 30)) return fail(PTG_E_INVALID, "ptg_tonemap: bad arguments");
-    PTG_HIP(ctx->grow(ctx->tmp_c, n * sizeof(float4)));
-    PTG_HIP(ctx->grow(ctx->tmp_a, n * sizeof(uchar4)));
-    PTG_HIP(hipMemcpyAsync(ctx->tmp_c.p, color, n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if(int r = launch_plain(ctx, grid_for(n), k_tonemap, uint32_t(n), ctx->tmp_c.as<float4>(), ctx->tmp_a.as<uchar4>())) return r;
-    PTG_HIP(hipMemcpyAsync(out, ctx->tmp_a.p, n * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
-    PTG_HIP(hipStreamSynchronize(ctx->stream));
-    return PTG_OK;
-}
-
 int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* rays, uint32_t* hits)
 {
     if(int r = bind(ctx)) return r;
@@ -3046,237 +2097,6 @@ int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uin
         return ptg_render_features(ctx, cfg, x0, y0, w, h, sample_begin, sample_end, out_albedo, out_normal_depth);
     }
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments, out_albedo, out_normal_depth);
-}
-
-void ptg_denoise_params_default(ptg_denoise_params* p)
-{
-    if(!p) return;
-    // the best row of tools/denoise_study.py's sweep (profiles/denoise_study/)
-    p->iterations = 4;
-    p->sigma_color = 2.0f;
-    p->sigma_albedo = 0.05f;
-    p->sigma_normal = 1.2f;
-    p->sigma_depth = 1.0f;
-    p->albedo_floor = 0.01f;
-}
-
-int ptg_denoise(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_params* params, const ptg_float4* radiance,
-                const ptg_float4* albedo, const ptg_float4* normal_depth, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
-{
-    if(int r = bind(ctx)) return r;
-    if(!params || !radiance || !albedo || !normal_depth || !out_radiance) return fail(PTG_E_INVALID, "ptg_denoise: null argument");
-    const ptg_denoise_params P = *params;
-    if(P.iterations > 8) return fail(PTG_E_INVALID, "ptg_denoise: more than 8 iterations");
-    for(float s: {P.sigma_color, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor})
-        if(!(s > 0.0f) || !std::isfinite(s)) return fail(PTG_E_INVALID, "ptg_denoise: sigmas and albedo_floor must be positive and finite");
-    const auto step_of = [&](uint32_t k) {
-        DenoiseStep a;
-        a.w = w; a.h = h; a.step = 1u << k;
-        const float sc = P.sigma_color * (1.0f / float(1u << k));   // sigma_color * 2^-k
-        a.var_color = sc * sc;
-        a.var_albedo = P.sigma_albedo * P.sigma_albedo;
-        a.var_normal = P.sigma_normal * P.sigma_normal;
-        a.var_depth = P.sigma_depth * P.sigma_depth;
-        return a;
-    };
-    return denoise_passes(ctx, w, h, P.iterations, P.albedo_floor, step_of, radiance, albedo, normal_depth, nullptr, out_radiance,
-                          out_bgra);
-}
-
-void ptg_denoise_guided_params_default(ptg_denoise_guided_params* p)
-{
-    if(!p) return;
-    // the best row of tools/denoise_study.py --guided --sweep (profiles/denoise_study/guided_study.json)
-    p->iterations = 3;
-    p->sigma_luminance = 0.5f;
-    p->sigma_albedo = 0.05f;
-    p->sigma_normal = 1.2f;
-    p->sigma_depth = 1.0f;
-    p->albedo_floor = 0.01f;
-    p->variance_floor = 1e-2f;
-}
-
-int ptg_denoise_guided(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_denoise_guided_params* params,
-                       const ptg_float4* radiance, const ptg_float4* albedo, const ptg_float4* normal_depth,
-                       const ptg_float4* moments, ptg_float4* out_radiance, ptg_uchar4* out_bgra)
-{
-    if(int r = bind(ctx)) return r;
-    if(!params || !radiance || !albedo || !normal_depth || !moments || !out_radiance)
-        return fail(PTG_E_INVALID, "ptg_denoise_guided: null argument");
-    const ptg_denoise_guided_params P = *params;
-    if(P.iterations > 8) return fail(PTG_E_INVALID, "ptg_denoise_guided: more than 8 iterations");
-    for(float s: {P.sigma_luminance, P.sigma_albedo, P.sigma_normal, P.sigma_depth, P.albedo_floor, P.variance_floor})
-        if(!(s > 0.0f) || !std::isfinite(s))
-            return fail(PTG_E_INVALID, "ptg_denoise_guided: sigmas and floors must be positive and finite");
-    const auto step_of = [&](uint32_t k) {
-        DenoiseGuidedStep a;
-        a.w = w; a.h = h; a.step = 1u << k;
-        a.sigma_luminance = P.sigma_luminance;
-        a.variance_floor = P.variance_floor;
-        a.var_albedo = P.sigma_albedo * P.sigma_albedo;
-        a.var_normal = P.sigma_normal * P.sigma_normal;
-        a.var_depth = P.sigma_depth * P.sigma_depth;
-        return a;
-    };
-    return denoise_passes(ctx, w, h, P.iterations, P.albedo_floor, step_of, radiance, albedo, normal_depth, moments, out_radiance,
-                          out_bgra);
-}
-
-void ptg_temporal_params_default(ptg_temporal_params* p)
-{
-    if(!p) return;
-    // the best row of tools/denoise_study.py --temporal --sweep (profiles/denoise_study/temporal_study.json)
-    p->max_history = 128.0f;
-    p->depth_tolerance = 0.02f;
-    p->normal_tolerance = 0.1f;
-    p->albedo_tolerance = 0.25f;
-}
-
-namespace {
-
-// What ptg_temporal_accumulate and ptg_temporal_accumulate_clamped check alike.
-// *given: the history is there (all five) or not (none); *empty: the image has
-// no pixel and the call is done.
-int temporal_check(const std::string& who, uint32_t w, uint32_t h, const ptg_temporal_params& P, const ptg_camera* hist_cam,
-                   const void* const hist[4], const void* out_radiance, const void* out_moments, bool* given_out, bool* empty)
-{
-    for(float s: {P.max_history, P.depth_tolerance, P.normal_tolerance, P.albedo_tolerance})
-        if(!(s > 0.0f) || !std::isfinite(s))
-            return fail(PTG_E_INVALID, who + ": max_history and the tolerances must be positive and finite");
-    int given = hist_cam ? 1 : 0;
-    for(int k = 0; k < 4; ++k) given += hist[k] ? 1 : 0;
-    if(given != 0 && given != 5)
-        return fail(PTG_E_INVALID, who + ": hist_cam and the four hist_* images are all null or all set");
-    if(out_radiance == out_moments) return fail(PTG_E_INVALID, who + ": out_radiance and out_moments are one buffer");
-    for(int k = 0; k < 4; ++k)
-        if(hist[k] && (hist[k] == out_radiance || hist[k] == out_moments))
-            return fail(PTG_E_INVALID, who + ": an output is a hist_* image (the history is gathered from neighbours)");
-    *given_out = given != 0;
-    *empty = uint64_t(w) * h == 0;
-    if(*empty) return PTG_OK;
-    // pixel coordinates are compared as floats: exact below 2^24
-    if(uint64_t(w) * h >= (1ull << 31) || w > (1u << 24) || h > (1u << 24)) return fail(PTG_E_RANGE, "image too large");
-    return PTG_OK;
-}
-
-TemporalCam temporal_cam_of(const ptg_camera& c)
-{
-    TemporalCam t;
-    for(int k = 0; k < 3; ++k) t.ori.r[k] = f3{c.orientation.r[k].x, c.orientation.r[k].y, c.orientation.r[k].z};
-    t.pos = f3{c.position.x, c.position.y, c.position.z};
-    t.aspect = c.aspect_ratio;
-    t.ifl = c.inv_focal_length;
-    t.fd = c.focal_distance;
-    return t;
-}
-
-const float4* tp_in(const ptg_float4* p) { return reinterpret_cast<const float4*>(p); }
-
-// What both temporal entries do once they have checked what is their own:
-// the common checks, the kernel's arguments, the launch.  `clamped`: the
-// clamped entry, with n_cams cameras in `cams` and every field of P; the plain
-// entry passes its one camera and P.base alone.
-int temporal_run(ptg_context* ctx, const std::string& who, bool clamped, uint32_t w, uint32_t h,
-                 const ptg_temporal_clamp_params& P, uint32_t n_cams, const ptg_camera* cams, const ptg_camera* hist_cam,
-                 const ptg_float4* radiance, const ptg_float4* moments, const ptg_float4* albedo, const ptg_float4* normal_depth,
-                 const ptg_float4* hist_radiance, const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
-                 const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments, ptg_uchar4* out_bgra,
-                 uint8_t* out_flags)
-{
-    const void* hist[4] = {hist_radiance, hist_moments, hist_albedo, hist_normal_depth};
-    bool given = false, empty = false;
-    if(int r = temporal_check(who, w, h, P.base, hist_cam, hist, out_radiance, out_moments, &given, &empty)) return r;
-    if(empty) return PTG_OK;
-    TemporalArgs a;
-    a.w = w; a.h = h;
-    a.has_history = given ? 1u : 0u;
-    a.max_history = P.base.max_history;
-    a.depth_tolerance = P.base.depth_tolerance;
-    a.normal_tolerance = P.base.normal_tolerance;
-    a.albedo_tolerance = P.base.albedo_tolerance;
-    a.cam = temporal_cam_of(cams[0]);
-    a.hist = temporal_cam_of(given ? *hist_cam : cams[0]);
-    a.n_cams = n_cams;
-    a.clamp_radius = P.clamp_radius;
-    a.clamp_sigma = P.clamp_sigma;
-    a.clipped_history = P.clipped_history;
-    const TemporalCam* dev_cams = nullptr;
-    if(clamped)
-    {
-        // The cameras go through a pinned staging buffer into the context's
-        // device buffer, on the context's stream.  The device buffer is safe
-        // against reuse by stream order: the next call's copy runs behind this
-        // call's kernel.  The staging buffers alternate, and one is written again
-        // only after the copy of two calls ago that read it has completed
-        // (HostStage::reserve waits for it).
-        PTG_HIP(ctx->grow(ctx->tp_cams, size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
-        HostStage& hs = ctx->tp_stage[ctx->tp_stage_next];
-        ctx->tp_stage_next ^= 1u;
-        PTG_HIP(hs.reserve(size_t(kTemporalMaxCams) * sizeof(TemporalCam)));
-        TemporalCam* staged = static_cast<TemporalCam*>(hs.p);
-        for(uint32_t k = 0; k < n_cams; ++k) staged[k] = temporal_cam_of(cams[k]);
-        PTG_HIP(hipMemcpyAsync(ctx->tp_cams.p, staged, size_t(n_cams) * sizeof(TemporalCam), hipMemcpyHostToDevice, ctx->stream));
-        PTG_HIP(hipEventRecord(hs.done, ctx->stream));
-        dev_cams = ctx->tp_cams.as<const TemporalCam>();
-    }
-    return launch_plain(ctx, grid_for(size_t(w) * h), clamped ? k_temporal_accumulate<true> : k_temporal_accumulate<false>, a,
-                        tp_in(radiance), tp_in(moments), tp_in(albedo), tp_in(normal_depth), tp_in(hist_radiance),
-                        tp_in(hist_moments), tp_in(hist_albedo), tp_in(hist_normal_depth),
-                        reinterpret_cast<float4*>(out_radiance), reinterpret_cast<float4*>(out_moments),
-                        reinterpret_cast<uchar4*>(out_bgra), dev_cams, out_flags);
-}
-
-} // namespace
-
-int ptg_temporal_accumulate(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_params* params,
-                            const ptg_camera* cam, const ptg_camera* hist_cam, const ptg_float4* radiance,
-                            const ptg_float4* moments, const ptg_float4* albedo, const ptg_float4* normal_depth,
-                            const ptg_float4* hist_radiance, const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
-                            const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments,
-                            ptg_uchar4* out_bgra)
-{
-    if(int r = bind(ctx)) return r;
-    if(!params || !cam || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
-        return fail(PTG_E_INVALID, "ptg_temporal_accumulate: null argument");
-    ptg_temporal_clamp_params P{};   // no clamp: the kernel's plain instantiation reads the base alone
-    P.base = *params;
-    return temporal_run(ctx, "ptg_temporal_accumulate", false, w, h, P, 1, cam, hist_cam, radiance, moments, albedo, normal_depth,
-                        hist_radiance, hist_moments, hist_albedo, hist_normal_depth, out_radiance, out_moments, out_bgra,
-                        nullptr);
-}
-
-void ptg_temporal_clamp_params_default(ptg_temporal_clamp_params* p)
-{
-    if(!p) return;
-    ptg_temporal_params_default(&p->base);
-    // the best row of tools/denoise_study.py --temporal-clamp --sweep (profiles/denoise_study/temporal_clamp_study.json)
-    p->clamp_radius = 1;
-    p->clamp_sigma = 2.0f;
-    p->clipped_history = 32.0f;
-}
-
-int ptg_temporal_accumulate_clamped(ptg_context* ctx, uint32_t w, uint32_t h, const ptg_temporal_clamp_params* params,
-                                    uint32_t n_cams, const ptg_camera* cams, const ptg_camera* hist_cam,
-                                    const ptg_float4* radiance, const ptg_float4* moments, const ptg_float4* albedo,
-                                    const ptg_float4* normal_depth, const ptg_float4* hist_radiance,
-                                    const ptg_float4* hist_moments, const ptg_float4* hist_albedo,
-                                    const ptg_float4* hist_normal_depth, ptg_float4* out_radiance, ptg_float4* out_moments,
-                                    ptg_uchar4* out_bgra, uint8_t* out_flags)
-{
-    static const std::string who = "ptg_temporal_accumulate_clamped";
-    if(int r = bind(ctx)) return r;
-    if(!params || !cams || !radiance || !moments || !albedo || !normal_depth || !out_radiance || !out_moments)
-        return fail(PTG_E_INVALID, who + ": null argument");
-    const ptg_temporal_clamp_params P = *params;
-    if(n_cams < 1 || n_cams > kTemporalMaxCams) return fail(PTG_E_INVALID, who + ": 1 .. 512 cameras");
-    if(P.clamp_radius > 2) return fail(PTG_E_INVALID, who + ": clamp_radius above 2");
-    for(float s: {P.clamp_sigma, P.clipped_history})
-        if(!(s > 0.0f) || !std::isfinite(s))
-            return fail(PTG_E_INVALID, who + ": clamp_sigma and clipped_history must be positive and finite");
-    if(P.clamp_radius > 0 && static_cast<const void*>(out_radiance) == static_cast<const void*>(radiance))
-        return fail(PTG_E_INVALID, who + ": out_radiance is radiance, which the clamp gathers from neighbours");
-    return temporal_run(ctx, who, true, w, h, P, n_cams, cams, hist_cam, radiance, moments, albedo, normal_depth, hist_radiance,
-                        hist_moments, hist_albedo, hist_normal_depth, out_radiance, out_moments, out_bgra, out_flags);
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

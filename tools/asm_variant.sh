@@ -34,6 +34,7 @@ sed -n '4,10p' cmds.txt | sed "s#/tmp/ptg_asm_base#$W#g" > steps.txt
 while read -r line; do eval "$line" 2>/dev/null || { echo "step failed: ${line:0:120}"; exit 1; }; done < steps.txt
 OUT="$PKG/_build/ablate_$TAG"
 mkdir -p "$OUT"
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT/libptg.so" "$PKG"/_build/obj/{mesh_loader,bvh_builder,host_trace,scene,block_bvh}.o $W/pk.o -pthread
+# (the image-space and upload units are the shipped build's: the same tree's sources, compiled by the make above)
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT/libptg.so" "$PKG"/_build/obj/{mesh_loader,bvh_builder,host_trace,scene,block_bvh,image_ops,upload}.o $W/pk.o -pthread
 cd / && rm -rf "$W"
 echo "$OUT/libptg.so"

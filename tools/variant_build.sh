@@ -15,8 +15,14 @@ python3 "$PATCH" "$W"
 OUT="$PKG/_build/ablate_$TAG"
 mkdir -p "$OUT"
 cd "$W"
-/opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
-  -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -I"$R/include" -I. "$@" -c pt_kernels.hip -o "$OUT/pt_kernels.o"
+# every HIP unit from the scratch copy: a variant never mixes units of two trees
+HIP_OBJS=""
+for u in pt_kernels image_ops upload; do
+  [ -f $u.hip ] || continue   # at_commit.py with a commit from before the split: that commit's units alone
+  /opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
+    -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -I"$R/include" -I. "$@" -c $u.hip -o "$OUT/$u.o"
+  HIP_OBJS="$HIP_OBJS $OUT/$u.o"
+done
 HOST_OBJS=$(echo "$PKG"/_build/obj/{mesh_loader,bvh_builder,host_trace,scene,block_bvh}.o)
 # the variant changes the host side too (e.g. -DPTG_BLOCK_WIDTH=8, or a whole
 # commit's sources: at_commit.py writes .rebuild_host): rebuild it from the
@@ -29,6 +35,6 @@ if [ -n "$HOST_FLAGS" ] || [ -f "$W/.rebuild_host" ]; then
     HOST_OBJS="$HOST_OBJS $OUT/$f.o"
   done
 fi
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT/libptg.so" $HOST_OBJS "$OUT/pt_kernels.o" -pthread
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT/libptg.so" $HOST_OBJS $HIP_OBJS -pthread
 rm -rf "$W"
 echo "$OUT/libptg.so"

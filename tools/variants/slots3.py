@@ -1,6 +1,6 @@
 # variant: three concurrent wavefront chunk pipelines instead of two
 import sys
-p = sys.argv[1] + "/pt_kernels.hip"
+p = sys.argv[1] + "/runtime.h"
 s = open(p).read()
 a = "constexpr uint32_t kWfSlots = 2;"
 assert a in s
