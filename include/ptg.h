@@ -247,6 +247,33 @@ int ptg_tonemap_device(ptg_context* ctx, size_t n, const ptg_float4* color, ptg_
  * is accepted. */
 int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* rays, uint32_t* hits);
 
+/* The same query through the kernels a render walks with: the wavefront
+ * pipeline's closest-hit and any-hit walk kernels, launched over the n rays as
+ * the queue of bounce round `round` (below 255) of subframe `subframe`, with
+ * the render's launch shape - or with grid_blocks workgroups (0: the
+ * context's own grid; above it: refused).  rays are 6 floats (origin.xyz,
+ * dir.xyz): tmin and tmax are the kernels' own for that round - closest hit:
+ * tmin 0 in round 0, MIN_RAY_DIST (1e-4) after it, tmax 1e9; any hit:
+ * MIN_RAY_DIST and MAX_RAY_DIST (1e9).  hits is ptg_trace_rays' record, except
+ * that word 2 is always 0 (the walk stores two barycentrics) and that words
+ * 0-2 are 0 on a miss.  A queue position that neither walk wrote fails the
+ * call (PTG_E_RANGE, the message names the position).
+ * counted != 0 runs the kernels' counting instantiations (same results) and
+ * fills stats[k] for the closest-hit (k = 0) and the any-hit walk (k = 1):
+ *   [0] walks started
+ *   [1] walks whose stack outgrew its on-chip window (part of it went to HBM)
+ *   [2] the largest stack size seen, in the stack's own units: 8-byte entries
+ *       in the closest-hit walk, 4-byte slots (one per entry) in the any-hit
+ *       walk; both windows hold 16 of them
+ *   [3] any-hit walks that began with the occluder a neighbouring ray found
+ * A counted run whose [2] is above what a walk lane's HBM area holds (the
+ * frame's stack bound in entries, twice that in slots) fails with
+ * PTG_E_RANGE.  stats may be null in a plain run, which zeroes it otherwise.  HOST pointers;
+ * synchronous; waits for the context's queued work first and changes nothing
+ * a render or ptg_last_* reports.  Used for ray-level parity of the walks. */
+int ptg_walk_rays(ptg_context* ctx, uint32_t subframe, uint32_t round, uint32_t grid_blocks, int counted,
+                  size_t n, const float* rays /* n x 6 */, uint32_t* hits /* n x 8 */, uint64_t stats[2][4]);
+
 /* The first ray path_trace_pixel traces for each (pixel, sample_index) pair:
  * the seed, the film jitter and get_camera_ray (path_tracer.hh:659-671,
  * :429-450).  rays gets 8 floats per pair, the layout ptg_trace_rays takes:

@@ -272,6 +272,15 @@ constexpr uint32_t kRedoGrid = 16;   // blocks of the MathExact shading passes (
 // lever on that level.
 enum WalkStat : int { WS_NODE_WAVES = 0, WS_NODE_LANES, WS_LEAF_WAVES, WS_LEAF_LANES, WS_REFILL_WAVES,
                       WS_REFILL_LANES, WS_ITERS, WS_ACTIVE_LANES, WS_COUNT };
+// Behind a walk kind's WS_COUNT words, per walk rather than per instruction
+// (ptg_walk_rays returns them; ptg_last_walk_stats keeps to the first
+// WS_COUNT): walks started; walks whose stack size passed the LDS window
+// (size() > kCap after a node phase, so part of the stack went to HBM and, in
+// the closest-hit walk, came back); the largest stack size seen, in the
+// stack's own units (LdsStack: entries, LdsSlotStack: slots); any-hit walks
+// that took the wave's candidate.  Tallied in k_wf_walk from outside the stack structs.
+enum WalkExtra : int { WX_STARTED = 0, WX_PAST_WINDOW, WX_MAX_SIZE, WX_CANDIDATES, WX_COUNT };
+constexpr int kWalkWords = WS_COUNT + WX_COUNT;   // a walk kind's words of wstats
 
 template<bool ANY, bool COUNT>
 __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, PathSoA S, const uint32_t* __restrict__ counts,
@@ -344,6 +353,8 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
         }
     };
     unsigned long long ws[WS_COUNT] = {};   // COUNT: lane 0's tallies for its wave
+    uint32_t wx[WX_COUNT] = {};             // COUNT: this lane's per-walk tallies (WalkExtra)
+    bool past_window = false;               // COUNT: this lane's walk has been counted in WX_PAST_WINDOW
     auto tally = [&](int waves_slot, bool loads) {
         const unsigned long long m = __ballot(loads);
         if(lane == 0 && m)
@@ -387,7 +398,13 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
                             if(ANY) w.try_candidate(sc, occ_inst, occ_prim, meta_sub(m));
                             active = true;
                             took = true;
-                            if(COUNT) cnt.queries++;
+                            if(COUNT)
+                            {
+                                cnt.queries++;
+                                wx[WX_STARTED]++;
+                                past_window = false;
+                                if(ANY && w.pend != kBePop) wx[WX_CANDIDATES]++;
+                            }
                         }
                     }
                 }
@@ -427,6 +444,16 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
                 r = 0;
             }
         }
+        if(COUNT && active)
+        {
+            const uint32_t size = w.st.size();
+            wx[WX_MAX_SIZE] = max(wx[WX_MAX_SIZE], size);
+            if(size > decltype(w.st)::kCap && !past_window)
+            {
+                past_window = true;
+                wx[WX_PAST_WINDOW]++;
+            }
+        }
         if(COUNT) cnt.step_loads = 0;
         bool occluded = false;
         if(active && w.wants_leaf())
@@ -453,6 +480,15 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
         if(lane == 0)
             for(int k = 0; k < WS_COUNT; ++k)
                 if(ws[k]) atomicAdd(wstats + k, ws[k]);
+        unsigned long long largest = wx[WX_MAX_SIZE];
+        for(int o = 32; o > 0; o >>= 1) largest = max(largest, (unsigned long long)__shfl_xor(largest, o));
+        for(int k = 0; k < WX_COUNT; ++k)
+        {
+            const unsigned long long v = k == WX_MAX_SIZE ? largest : wave_sum(wx[k]);
+            if(lane != 0 || !v) continue;
+            if(k == WX_MAX_SIZE) atomicMax(wstats + WS_COUNT + k, v);
+            else atomicAdd(wstats + WS_COUNT + k, v);
+        }
     }
 }
 
@@ -1126,9 +1162,9 @@ int check_cfg(const ptg_context* ctx, const ptg_render_config* cfg, uint32_t sam
 enum Kind : int { K_MEGA = 0, K_EXTEND = 1, K_SHADOW = 2, K_SHADE = 3, K_CAMERA = 4, K_ACCUM = 5, K_KINDS = 6,
                   K_SKY = 6, K_CLASSIFY = 7 };
 // counting builds' device counters: 8 per kernel kind, the walk statistics
-// (WS_COUNT each for the closest-hit and the any-hit walk), then the
+// (kWalkWords each for the closest-hit and the any-hit walk), then the
 // certified shading's redo tallies (kRedoWords, tally_redo)
-constexpr int kCounterWords = K_KINDS * 8 + 2 * WS_COUNT + kRedoWords;
+constexpr int kCounterWords = K_KINDS * 8 + 2 * kWalkWords + kRedoWords;
 
 int timed_begin(ptg_context* ctx, int kind, hipStream_t st = nullptr)
 {
@@ -1219,8 +1255,8 @@ struct RenderJob {
     bool first_camera_queued = false;      // ctx->ev_first_camera is recorded in this render
 
     unsigned long long* cnt_for(int kind) const { return cnt ? cnt + 8 * kind : nullptr; }
-    unsigned long long* ws_for(bool any) const { return cnt ? cnt + 8 * K_KINDS + (any ? WS_COUNT : 0) : nullptr; }
-    unsigned long long* redo_tally() const { return cnt ? cnt + 8 * K_KINDS + 2 * WS_COUNT : nullptr; }
+    unsigned long long* ws_for(bool any) const { return cnt ? cnt + 8 * K_KINDS + (any ? kWalkWords : 0) : nullptr; }
+    unsigned long long* redo_tally() const { return cnt ? cnt + 8 * K_KINDS + 2 * kWalkWords : nullptr; }
     // walk stack spill areas: one per (chunk pipeline, walk kind), since up to
     // four walk launches run at once; stack_bound entries per walk lane
     DevScene walk_scene(uint32_t slot, int kind) const
@@ -1555,8 +1591,9 @@ int read_counters(ptg_context* ctx)
     unsigned long long host[kCounterWords];
     PTG_HIP(hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
-    for(int k = 0; k < 2 * WS_COUNT; ++k) ctx->walk_stats[k / WS_COUNT][k % WS_COUNT] = host[K_KINDS * 8 + k];
-    for(int k = 0; k < kRedoWords; ++k) ctx->redo_stats[k] = host[K_KINDS * 8 + 2 * WS_COUNT + k];
+    for(int w = 0; w < 2; ++w)   // (the WalkExtra words behind them are ptg_walk_rays' alone)
+        for(int k = 0; k < WS_COUNT; ++k) ctx->walk_stats[w][k] = host[K_KINDS * 8 + w * kWalkWords + k];
+    for(int k = 0; k < kRedoWords; ++k) ctx->redo_stats[k] = host[K_KINDS * 8 + 2 * kWalkWords + k];
     for(int i = 0; i < 8; ++i)
     {
         ctx->last_counters[i] = 0;
@@ -2033,6 +2070,142 @@ int ptg_trace_rays(ptg_context* ctx, uint32_t subframe, size_t n, const float* r
         return r;
     PTG_HIP(hipMemcpyAsync(hits, ctx->tmp_b.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     PTG_HIP(hipStreamSynchronize(ctx->stream));
+    return PTG_OK;
+}
+
+// The render's walk kernels over a caller's rays: one PathSoA half with the
+// fields k_wf_walk reads (meta, ray_o, ray_d = nee_d), a queue of n positions
+// in round `round`, an identity NEE list and a TraceOut, all in walk_state;
+// then the two launches of trace_chunk_wavefront, untimed, on the context's
+// stream.  Nothing of a render is touched: the streams are drained first, and
+// the counters and statistics of a counted run are the call's own.
+int ptg_walk_rays(ptg_context* ctx, uint32_t subframe, uint32_t round, uint32_t grid_blocks, int counted, size_t n,
+                  const float* rays, uint32_t* hits, uint64_t stats[2][4])
+{
+    if(int r = bind(ctx)) return r;
+    if(!ctx->scene_ready || !ctx->frame_ready) return fail(PTG_E_INVALID, "scene/frame not uploaded");
+    if(subframe >= ctx->subframe_count) return fail(PTG_E_RANGE, "subframe out of range");
+    if(round >= 255) return fail(PTG_E_RANGE, "ptg_walk_rays: round " + std::to_string(round) + " (below 255)");
+    uint32_t grid[2], xcds[2];
+    for(int k = 0; k < 2; ++k)
+    {
+        if(grid_blocks > ctx->walk_grid[k])
+            return fail(PTG_E_RANGE, "ptg_walk_rays: grid_blocks " + std::to_string(grid_blocks) + " above the context's walk grid " +
+                                         std::to_string(ctx->walk_grid[k]));
+        grid[k] = grid_blocks ? grid_blocks : ctx->walk_grid[k];
+        xcds[k] = grid_blocks ? ((grid[k] % 8 == 0 && kBands % 8 == 0) ? 8u : 1u) : ctx->walk_xcds[k];
+    }
+    if(counted && !stats) return fail(PTG_E_INVALID, "ptg_walk_rays: a counted run needs stats");
+    if(!n) return PTG_OK;
+    if(!rays || !hits || n >= (1u << 28)) return fail(PTG_E_INVALID, "ptg_walk_rays: bad arguments");
+    if(ctx->host_tri_base.size() != ctx->instance_count) return fail(PTG_E_INVALID, "ptg_walk_rays: no triangle bases for this frame");
+    PTG_HIP(ctx->drain());
+
+    // walk_state: meta, origins, directions (16 B each per position), hit
+    // (16), bary (8), shadow and list (4 each), then the counts and, 8-byte
+    // aligned, a counted run's counters (8 per kind) and statistics
+    const size_t count_words = (2 * size_t(round) + 2 + 1) & ~size_t(1);
+    const size_t stat_words = 2 * (8 + kWalkWords);
+    const size_t bytes = n * (3 * 16 + 16 + 8 + 4 + 4) + count_words * 4 + stat_words * 8;
+    PTG_HIP(ctx->grow(ctx->walk_state, bytes));
+    char* base = ctx->walk_state.as<char>();
+    PathSoA S{};
+    TraceOut tr{};
+    S.meta = reinterpret_cast<uint4*>(base);
+    S.ray_o = reinterpret_cast<float4*>(base + n * 16);
+    S.ray_d = S.nee_d = reinterpret_cast<float4*>(base + n * 32);
+    tr.hit = reinterpret_cast<uint4*>(base + n * 48);
+    tr.bary = reinterpret_cast<float2*>(base + n * 64);
+    tr.shadow = reinterpret_cast<uint32_t*>(base + n * 72);
+    uint32_t* list = reinterpret_cast<uint32_t*>(base + n * 76);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(base + n * 80);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(base + n * 80 + count_words * 4);
+
+    std::vector<uint32_t> host, out;   // meta, origins, directions, the list, the counts; hit, bary, shadow
+    try
+    {
+        host.assign(n * 13 + count_words, 0u);
+        out.assign(n * 7, 0u);
+    }
+    catch(const std::bad_alloc&)
+    {
+        return fail(PTG_E_NOMEM, "ptg_walk_rays: host memory");
+    }
+    uint32_t* h_meta = host.data();
+    uint32_t *h_o = h_meta + n * 4, *h_d = h_o + n * 4, *h_list = h_d + n * 4, *h_counts = h_list + n;
+    // meta_pack(round, true, subframe) (a device function) and the TLAS root k_wf_camera writes
+    const uint32_t meta_y = round | 0x100u | (subframe << 16), root = ctx->host_tlas_root[subframe];
+    for(size_t i = 0; i < n; ++i)
+    {
+        const uint32_t m[4] = {uint32_t(i), meta_y, root, 0u};
+        memcpy(h_meta + i * 4, m, 16);
+        memcpy(h_o + i * 4, rays + i * 6, 12);
+        memcpy(h_d + i * 4, rays + i * 6 + 3, 12);
+        h_list[i] = uint32_t(i);
+    }
+    h_counts[2 * round] = h_counts[2 * round + 1] = uint32_t(n);
+    hipStream_t st = ctx->stream;
+    PTG_HIP(hipMemcpyAsync(base, h_meta, n * 48, hipMemcpyHostToDevice, st));
+    PTG_HIP(hipMemcpyAsync(list, h_list, n * 4, hipMemcpyHostToDevice, st));
+    PTG_HIP(hipMemcpyAsync(counts, h_counts, count_words * 4, hipMemcpyHostToDevice, st));
+    PTG_HIP(hipMemsetAsync(cnt, 0, stat_words * 8, st));
+    // a result the walks do not write keeps the sentinel: hit, bary and shadow are one range
+    constexpr uint32_t kSentinel = 0xDEADBEEFu;
+    PTG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tr.hit), int(kSentinel), n * 7, st));
+
+    const size_t region = size_t(std::max(grid[0], grid[1])) * kBlock * ctx->stack_bound;
+    PTG_HIP(ctx->grow(ctx->spill, std::max<size_t>(1, 2 * region) * sizeof(uint2)));
+    DevScene sc[2] = {ctx->scene_args(nullptr), ctx->scene_args(nullptr)};
+    sc[0].spill = ctx->spill.as<uint2>();
+    sc[1].spill = ctx->spill.as<uint2>() + region;
+    unsigned long long* kc[2] = {counted ? cnt : nullptr, counted ? cnt + 8 : nullptr};
+    unsigned long long* ws[2] = {counted ? cnt + 16 : nullptr, counted ? cnt + 16 + kWalkWords : nullptr};
+    const uint32_t* no_list = nullptr;
+    const auto closest = counted ? k_wf_walk<false, true> : k_wf_walk<false, false>;
+    const auto any = counted ? k_wf_walk<true, true> : k_wf_walk<true, false>;
+    hipLaunchKernelGGL(closest, dim3(grid[0]), dim3(kBlock), ctx->walk_lds[0], st, sc[0], S, counts, round, no_list, tr, xcds[0],
+                       kc[0], ws[0]);
+    PTG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(any, dim3(grid[1]), dim3(kBlock), ctx->walk_lds[1], st, sc[1], S, counts, round, list, tr, xcds[1], kc[1],
+                       ws[1]);
+    PTG_HIP(hipGetLastError());
+
+    unsigned long long h_stats[2 * (8 + kWalkWords)];
+    PTG_HIP(hipMemcpyAsync(out.data(), tr.hit, n * 28, hipMemcpyDeviceToHost, st));
+    PTG_HIP(hipMemcpyAsync(h_stats, cnt, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+    PTG_HIP(hipStreamSynchronize(st));
+    const uint32_t *o_hit = out.data(), *o_bary = o_hit + n * 4, *o_shadow = o_bary + n * 2;
+    for(size_t i = 0; i < n; ++i)
+    {
+        const uint32_t* h = o_hit + i * 4;
+        const bool miss = h[1] == 0xFFFFFFFFu;
+        if(h[0] == kSentinel || o_shadow[i] == kSentinel || (!miss && o_bary[2 * i] == kSentinel && o_bary[2 * i + 1] == kSentinel))
+            return fail(PTG_E_RANGE, "ptg_walk_rays: queue position " + std::to_string(i) + " of " + std::to_string(n) +
+                                         " was not written by the " + (o_shadow[i] == kSentinel ? "any-hit" : "closest-hit") +
+                                         " walk (grid " + std::to_string(grid[0]) + " / " + std::to_string(grid[1]) + ")");
+        if(!miss && (h[1] >= ctx->instance_count || h[2] < ctx->host_tri_base[h[1]]))
+            return fail(PTG_E_RANGE, "ptg_walk_rays: position " + std::to_string(i) + " names instance " + std::to_string(h[1]) +
+                                         ", triangle " + std::to_string(h[2]));
+        uint32_t* w = hits + i * 8;
+        w[0] = miss ? 0u : o_bary[2 * i];
+        w[1] = miss ? 0u : o_bary[2 * i + 1];
+        w[2] = 0u;
+        w[3] = h[0];
+        w[4] = h[1];
+        w[5] = miss ? h[2] : h[2] - ctx->host_tri_base[h[1]];   // mesh-global -> mesh-local
+        w[6] = h[3];
+        w[7] = o_shadow[i];
+    }
+    if(stats)
+        for(int k = 0; k < 2; ++k)
+            for(int j = 0; j < WX_COUNT; ++j) stats[k][j] = counted ? h_stats[16 + k * kWalkWords + WS_COUNT + j] : 0;
+    // a lane's spill area holds stack_bound 8-byte entries: 2 * stack_bound slots of a slot stack
+    const uint64_t room[2] = {uint64_t(ctx->stack_bound) * (std::is_same<WalkStackOf<false>::type, LdsStack>::value ? 1 : 2),
+                              uint64_t(ctx->stack_bound) * (std::is_same<WalkStackOf<true>::type, LdsStack>::value ? 1 : 2)};
+    for(int k = 0; counted && k < 2; ++k)
+        if(stats[k][WX_MAX_SIZE] > room[k])
+            return fail(PTG_E_RANGE, std::string("ptg_walk_rays: the ") + (k ? "any-hit" : "closest-hit") + " walk's stack reached " +
+                                         std::to_string(stats[k][WX_MAX_SIZE]) + ", its spill area holds " + std::to_string(room[k]));
     return PTG_OK;
 }
 

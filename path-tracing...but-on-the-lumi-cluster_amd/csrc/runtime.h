@@ -115,6 +115,7 @@ struct ptg_context {
     size_t block_count = 0, subframe_count = 0, instance_count = 0;
     uint32_t stack_bound = 0;                            // TLAS + BLAS stack bound of this frame (entries)
     std::vector<uint32_t> host_tlas_root;
+    std::vector<uint32_t> host_tri_base;                 // per instance: its mesh's first triangle (TraceOut names mesh-global triangles)
     bool frame_ready = false;
 
     // ---- the image-space unit ----
@@ -131,6 +132,7 @@ struct ptg_context {
     ptg::DevBuf mom;                       // ptg_render_moments: the running (s1, s2, n) per pixel, beside acc
     ptg::DevBuf feat_acc;                  // ptg_render_with_features: the eight running feature sums per pixel (k_fold_features)
     ptg::DevBuf feat_spill;                // ptg_render_features: the walk stacks' spill areas
+    ptg::DevBuf walk_state;                // ptg_walk_rays: its queue, path state, results and statistics
     ptg::DevBuf ad_list, ad_count;         // ptg_render_adaptive: the active pixels' ids and their number
     uint32_t ad_passes_run = 0;            // ptg_last_adaptive_stats
     uint64_t ad_active[16] = {};

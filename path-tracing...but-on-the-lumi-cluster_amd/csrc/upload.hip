@@ -221,6 +221,8 @@ int upload_frame(ptg_context* ctx, const ptg_subframe* subframes, size_t subfram
     ctx->block_count = fp.total_blocks();
     ctx->stack_bound = fp.stack_bound();
     ctx->host_tlas_root = fp.tlas_root;
+    ctx->host_tri_base.resize(instance_count);
+    for(size_t i = 0; i < instance_count; ++i) ctx->host_tri_base[i] = fp.inst_shade[i].index_offset / 3;
     ctx->subframe_count = subframe_count;
     ctx->instance_count = instance_count;
     ctx->frame_ready = true;

@@ -132,6 +132,7 @@ def lib():
         "ptg_tonemap": (I, [P, SZ, P, P]),
         "ptg_tonemap_device": (I, [P, SZ, P, P]),
         "ptg_trace_rays": (I, [P, U32, SZ, P, P]),
+        "ptg_walk_rays": (I, [P, U32, U32, U32, I, SZ, P, P, P]),
         "ptg_camera_rays": (I, [P, P, SZ, P, P, P, P]),
         "ptg_render_features": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P]),
         "ptg_denoise_params_default": (None, [P]),

@@ -130,6 +130,18 @@ class GpuRenderer:
                 "ptg_trace_rays")
         return hits
 
+    def walk_rays(self, subframe: int, rays: np.ndarray, round: int = 0, grid_blocks: int = 0, counted: bool = False):
+        """The render's walk kernels over `rays` (float32 [n, 6]: origin,
+        direction) as bounce round `round`'s queue (ptg_walk_rays):
+        (hits uint32 [n, 8] in trace_rays' layout, stats uint64 [2, 4] of a
+        counted run or None)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        hits = np.zeros((len(rays), 8), np.uint32)
+        stats = np.zeros((2, 4), np.uint64)
+        N.check(N.lib().ptg_walk_rays(self._ctx, subframe, round, grid_blocks, int(bool(counted)), len(rays),
+                                      rays.ctypes.data, hits.ctypes.data, stats.ctypes.data), "ptg_walk_rays")
+        return hits, (stats if counted else None)
+
     def camera_rays(self, cfg, xy: np.ndarray, sample_index: np.ndarray):
         """The first ray of each (pixel, sample) pair (ptg_camera_rays):
         (rays float32 [n, 8] in trace_rays' layout, subframe uint32 [n])."""

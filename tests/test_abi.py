@@ -59,6 +59,16 @@ def test_gpu_entry_points_reject_null_context(native_lib):
     assert native_lib.ptg_render(None, C.byref(cfg), 0, 0, 1, 1, 0, 1, None, None) == -1
     assert native_lib.ptg_upload_frame(None, None, 0, None, 0, None, None, 0, 0) == -1
     assert native_lib.ptg_synchronize(None) == -1
+    assert native_lib.ptg_trace_rays(None, 0, 0, None, None) == -1
+    assert native_lib.ptg_walk_rays(None, 0, 0, 0, 0, 0, None, None, None) == -1
+
+
+def test_parity_entries_are_declared_and_bound(native_lib):
+    """The per-ray parity entries: the per-lane walker's and the wavefront walk kernels'."""
+    for f in ("ptg_trace_rays", "ptg_walk_rays", "ptg_camera_rays", "ptg_path_trace_samples"):
+        assert f in declared_functions() and f in N.exported_symbols()
+        assert getattr(native_lib, f).argtypes
+    assert len(native_lib.ptg_walk_rays.argtypes) == 9
 
 
 def test_context_create_without_gpu_fails_loudly(native_lib):
