@@ -554,6 +554,92 @@ int ptg_render_adaptive(ptg_context* ctx, const ptg_render_config* cfg,
  * it took are the sum of active[k] * N / passes. */
 int ptg_last_adaptive_stats(ptg_context* ctx, uint32_t* passes_run, uint64_t active[16]);
 
+/* ---- progressive rendering: a resumable sample accumulator ----------------
+ * ptg_render_with_features in steps.  The running per-pixel sums that the
+ * render entries keep inside the context and divide on their last chunk are
+ * here a DEVICE buffer the caller owns (`state`), described by a small HOST
+ * header (ptg_accum): ptg_accum_add traces the next samples into it,
+ * ptg_accum_resolve divides and tonemaps a copy at any time without ending the
+ * accumulation, and the two together are a checkpoint: a state copied out,
+ * kept in a file and put back, in this or another context or process,
+ * continues to the bits of the one-shot render, because every sum goes on in
+ * sample order from the very float32 values the one-shot render would hold at
+ * that sample.
+ *
+ * State layout (the checkpoint format).  `planes` planes of [h][w] ptg_float4,
+ * row-major over the rectangle (pixel (x0+i, y0+k) at row k, column i), one
+ * after the other:
+ *   plane 0                   the radiance sums (ax, ay, az, 0)
+ *   with PTG_ACCUM_MOMENTS    one plane (s1, s2, n, 0): the luminance sums of
+ *                             ptg_render_moments over the finite samples, n a
+ *                             uint32 stored in the float's bits
+ *   with PTG_ACCUM_FEATURES   two planes: (sum albedo.rgb, sum coverage), then
+ *                             (sum normal.xyz, sum depth) of ptg_render_features
+ * Every sum is float32, in sample order from +0; a fresh state is all-zero
+ * bytes. */
+#define PTG_ACCUM_MOMENTS  1u   /* keep the luminance moments (s1, s2, n) */
+#define PTG_ACCUM_FEATURES 2u   /* keep the eight first-hit feature sums */
+#define PTG_ACCUM_MAGIC    0x41475450u   /* 'PTGA' */
+#define PTG_ACCUM_VERSION  1u
+typedef struct {                /* 64 bytes, HOST; written by ptg_accum_begin / _add only */
+    uint32_t magic, version;    /* PTG_ACCUM_MAGIC, PTG_ACCUM_VERSION */
+    ptg_render_config cfg;      /* the configuration every add uses */
+    uint32_t x0, y0, w, h;      /* rectangle (no tile set) */
+    uint32_t flags;             /* PTG_ACCUM_* */
+    uint32_t sample_begin, sample_next;   /* the state holds samples [sample_begin, sample_next) */
+    uint32_t reserved;          /* 0 */
+} ptg_accum;
+#ifdef __cplusplus
+static_assert(sizeof(ptg_accum) == 64, "ptg_accum is 16 words");
+#else
+_Static_assert(sizeof(ptg_accum) == 64, "ptg_accum is 16 words");
+#endif
+/* Bytes of a state: planes * w * h * 16, planes = 1 + (MOMENTS: 1) +
+ * (FEATURES: 2); 0 for unknown flag bits. */
+size_t ptg_accum_state_bytes(uint32_t w, uint32_t h, uint32_t flags);
+/* Start an accumulation over a rectangle: the configuration and the rectangle
+ * are checked as ptg_render checks them (a scene and a frame are uploaded),
+ * unknown flag bits are PTG_E_INVALID.  Fills *acc (sample_next =
+ * sample_begin) and zeroes `state` (ptg_accum_state_bytes bytes, DEVICE)
+ * asynchronously on the context's stream. */
+int ptg_accum_begin(ptg_context* ctx, const ptg_render_config* cfg,
+                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                    uint32_t flags, uint32_t sample_begin, ptg_accum* acc, void* state /* DEVICE */);
+/* Trace samples [acc->sample_next, sample_end) of the frame now uploaded and
+ * add them to the state in sample order, then set acc->sample_next =
+ * sample_end.  The pipeline, concurrency level, chunk size and counting mode
+ * are the context's; for ptg_last_* and the timing record the call counts as
+ * a ptg_render* call.  Asynchronous on the context's stream.
+ * CONTRACT, not checked: the scene and the frame uploaded are the same at
+ * every add of one accumulation, and `state` is the buffer of that header
+ * (or a copy of its bytes).  Nothing ties a state to a frame.
+ * A header with a bad magic or version, sample_end <= acc->sample_next, or
+ * PTG_ACCUM_FEATURES under ptg_set_pipeline(ctx, 1) (the megakernel keeps no
+ * per-sample features) is PTG_E_INVALID; a range the frame has too few
+ * subframes for is ptg_render's PTG_E_RANGE.  A refused call launches nothing
+ * and leaves header and state untouched.  Without PTG_ACCUM_FEATURES it runs
+ * on both pipelines. */
+int ptg_accum_add(ptg_context* ctx, ptg_accum* acc, void* state /* DEVICE */, uint32_t sample_end);
+/* Read the state, change nothing in it, and write any subset of the five
+ * outputs (at least one; DEVICE pointers, [h][w] each).
+ * by_samples == 0: every sum is divided by (float)cfg.samples_per_pixel, so
+ *   the outputs are the bits of ptg_render_with_features(cfg, rectangle,
+ *   sample_begin, sample_next, ...) on the same frame - without
+ *   PTG_ACCUM_MOMENTS, out_accum and out_bgra are ptg_render's.  No arithmetic
+ *   of its own is defined.
+ * by_samples != 0: the radiance and the eight feature sums are divided by
+ *   (float)(sample_next - sample_begin) instead: a preview at the final
+ *   brightness.  out_bgra is tonemap_pixel of the radiance written; the
+ *   moments, normalised by n, are the same in both modes.
+ * An empty state (sample_next == sample_begin), a bad header, out_moments
+ * without PTG_ACCUM_MOMENTS, out_albedo or out_normal_depth without
+ * PTG_ACCUM_FEATURES, two outputs that are the same buffer, or an output that
+ * overlaps the state is PTG_E_INVALID and launches nothing.  Needs no scene.
+ * Asynchronous on the context's stream. */
+int ptg_accum_resolve(ptg_context* ctx, const ptg_accum* acc, const void* state /* DEVICE */, int by_samples,
+                      ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments,
+                      ptg_float4* out_albedo, ptg_float4* out_normal_depth);
+
 /* Work counters of the last ptg_render* call (filled only while counting is
  * on, ptg_counters_enable; counting uses a separate, slower build of the
  * kernels):

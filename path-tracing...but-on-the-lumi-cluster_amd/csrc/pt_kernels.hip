@@ -24,6 +24,9 @@
 //                   adaptive sampling (ptg_render_adaptive): the stopping rule
 //                   compacted into a pixel list, the fold over that list, the
 //                   final division (its camera is k_wf_camera over AdaptivePass)
+//   k_accum_resolve progressive rendering (ptg_accum_*): the caller's running
+//                   sums divided and tonemapped without ending the accumulation
+//                   (its folds are k_accumulate and k_fold_features themselves)
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
@@ -1138,6 +1141,48 @@ __global__ __launch_bounds__(kBlock) void k_ad_resolve(uint32_t npix, const floa
     if(out_samples) out_samples[p] = ns;
 }
 
+// ptg_accum_resolve, one work-item per rectangle pixel: the caller's planes
+// (ptg.h's state layout: acc, then mom and the two planes of feat where the
+// state has them) closed as the folds' last chunk closes the context's sums -
+// each sum / div in one rounding (k_accumulate's and k_fold_features' last
+// branch, div = spp there), tonemap of the radiance written, moments_of the
+// luminance sums.  The planes are only read.  Each output may be null; a
+// null output's plane is not loaded (mom and feat may then be null too).
+__global__ __launch_bounds__(kBlock) void k_accum_resolve(uint32_t npix, const float4* __restrict__ acc,
+                                                          const float4* __restrict__ mom,
+                                                          const float4* __restrict__ feat, float div,
+                                                          float4* __restrict__ out_accum, uchar4* __restrict__ out_bgra,
+                                                          float4* __restrict__ out_moments,
+                                                          float4* __restrict__ out_albedo,
+                                                          float4* __restrict__ out_normal_depth)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= npix) return;
+    if(out_accum || out_bgra)
+    {
+        const float4 a = acc[p];
+        const float ax = a.x / div, ay = a.y / div, az = a.z / div;
+        if(out_accum) out_accum[p] = make_float4(ax, ay, az, 0.f);
+        if(out_bgra) out_bgra[p] = tonemap(V3(ax, ay, az));
+    }
+    if(out_moments)
+    {
+        const float4 mo = mom[p];
+        const uint32_t n = __float_as_uint(mo.z);
+        out_moments[p] = n > 0 ? moments_of(mo.x, mo.y, n) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if(out_albedo)
+    {
+        const float4 a = feat[p];
+        out_albedo[p] = make_float4(a.x / div, a.y / div, a.z / div, a.w / div);
+    }
+    if(out_normal_depth)
+    {
+        const float4 n = feat[npix + p];
+        out_normal_depth[p] = make_float4(n.x / div, n.y / div, n.z / div, n.w / div);
+    }
+}
+
 // ---------------------------------------------------------- render driver --
 
 int check_cfg(const ptg_context* ctx, const ptg_render_config* cfg, uint32_t sample_end)
@@ -1214,6 +1259,16 @@ int launch(ptg_context* ctx, int kind, hipStream_t st, dim3 grid, uint32_t lds, 
     return timed_end(ctx, st);
 }
 
+// The running sums of a progressive render (ptg_accum_*), which belong to the
+// caller: the planes of ptg.h's state layout, laid out and summed as the
+// context's own acc, mom and feat_acc are.  mom and feat are null where the
+// state has no such plane.
+struct FoldPlanes {
+    float4* acc = nullptr;    // the radiance sums
+    float4* mom = nullptr;    // (s1, s2, n as bits, 0)
+    float4* feat = nullptr;   // two planes: albedo + coverage, normal + depth
+};
+
 // A render call's fixed parts, shared by the steps render_map and
 // render_adaptive are made of.
 struct RenderJob {
@@ -1237,7 +1292,12 @@ struct RenderJob {
     // ptg_render_with_features on the wavefront pipeline (both or neither): round 0
     // stores the first-hit features per sample, fold_chunk folds them too
     float4 *out_albedo = nullptr, *out_normal_depth = nullptr;
-    bool fused() const { return out_albedo != nullptr; }
+    // ptg_accum_add: fold into these planes, the caller's, and do not resolve
+    // (fold_chunk); with keep.mom the fold keeps the moments, with keep.feat
+    // the render is a fused one
+    FoldPlanes keep;
+    bool moments() const { return out_moments != nullptr || keep.mom != nullptr; }
+    bool fused() const { return out_albedo != nullptr || keep.feat != nullptr; }
     // slot k's per-sample feature arrays, each pm.npix * chunk entries
     FeatOut<true> feat_of(uint32_t k) const
     {
@@ -1540,24 +1600,29 @@ int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
     ptg_context::Slot& sl = ctx->slot[pc.slot];
-    const int first = pc.j == job.j0, last = pc.j + pc.n >= job.j1;
+    // ptg_accum_add (job.keep): the sums are the caller's planes and no chunk
+    // is the first or the last - the fold reads them, adds and writes them back
+    // (a zeroed plane starts from +0 as `first` does), and divides nothing
+    const bool kept = job.keep.acc != nullptr;
+    const int first = !kept && pc.j == job.j0, last = !kept && pc.j + pc.n >= job.j1;
+    float4* const acc = kept ? job.keep.acc : ctx->acc.as<float4>();
+    float4* const mom = kept ? job.keep.mom : ctx->mom.as<float4>();
+    float4* const facc = kept ? job.keep.feat : ctx->feat_acc.as<float4>();
     const hipStream_t as = ctx->main_of(pc.slot);
     if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
         PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
-    const auto fold = job.out_moments ? k_accumulate<true> : k_accumulate<false>;
+    const auto fold = job.moments() ? k_accumulate<true> : k_accumulate<false>;
     const dim3 grid(grid_for(job.pm.npix));
     if(int r = job.ad ? launch(ctx, K_ACCUM, as, grid, 0, k_ad_fold, k_ad_fold, *job.ad, pc.n, sl.samples.as<float4>(),
                                ctx->acc.as<float4>(), ctx->mom.as<float4>())
-                      : launch(ctx, K_ACCUM, as, grid, 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(),
-                               ctx->acc.as<float4>(), ctx->mom.as<float4>(), first, last,
-                               (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
+                      : launch(ctx, K_ACCUM, as, grid, 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(), acc, mom, first,
+                               last, (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
         return r;
     if(job.fused())
     {   // the features of the chunk, directly behind its samples: same stream, same order, same event
         const FeatOut<true> f = job.feat_of(pc.slot);
         if(int r = launch(ctx, K_ACCUM, as, grid, 0, k_fold_features, k_fold_features, job.pm, pc.n, f.albedo, f.normal_depth,
-                          ctx->feat_acc.as<float4>(), first, last, (float)job.cfg->samples_per_pixel, job.out_albedo,
-                          job.out_normal_depth))
+                          facc, first, last, (float)job.cfg->samples_per_pixel, job.out_albedo, job.out_normal_depth))
             return r;
     }
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
@@ -1663,9 +1728,12 @@ int join_folds(const RenderJob& job)
 // With out_albedo / out_normal_depth (wavefront only: ptg_render_with_features)
 // round 0 also stores every sample's first-hit features and k_fold_features
 // folds them.
+// With `keep` (ptg_accum_add; no outputs beside it) the chunks fold into the
+// caller's planes, moments and features as the planes say, and nothing is
+// resolved: the context's own sums are not touched.
 int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
                ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments = nullptr,
-               ptg_float4* out_albedo = nullptr, ptg_float4* out_normal_depth = nullptr)
+               ptg_float4* out_albedo = nullptr, ptg_float4* out_normal_depth = nullptr, const FoldPlanes* keep = nullptr)
 {
     if(pm.npix == 0) return PTG_OK;
     if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
@@ -1680,10 +1748,15 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
         job.out_albedo = reinterpret_cast<float4*>(out_albedo);
         job.out_normal_depth = reinterpret_cast<float4*>(out_normal_depth);
     }
+    if(keep)
+    {
+        if(keep->feat && !wf) return fail(PTG_E_INVALID, "render_map: fused features run on the wavefront pipeline");
+        job.keep = *keep;
+    }
     if(int r = begin_render(job, wf)) return r;
     if(int r = size_chunks(job, wf)) return r;
-    PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
-    if(job.fused()) PTG_HIP(ctx->grow(ctx->feat_acc, 2 * size_t(pm.npix) * sizeof(float4)));
+    if(!keep) PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
+    if(job.fused() && !keep) PTG_HIP(ctx->grow(ctx->feat_acc, 2 * size_t(pm.npix) * sizeof(float4)));
     if(out_moments)
     {
         job.out_moments = reinterpret_cast<float4*>(out_moments);
@@ -2270,6 +2343,120 @@ int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uin
         return ptg_render_features(ctx, cfg, x0, y0, w, h, sample_begin, sample_end, out_albedo, out_normal_depth);
     }
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments, out_albedo, out_normal_depth);
+}
+
+// ---- progressive rendering (ptg_accum_*) ----
+
+static uint32_t accum_plane_count(uint32_t flags)
+{
+    return 1u + (flags & PTG_ACCUM_MOMENTS ? 1u : 0u) + (flags & PTG_ACCUM_FEATURES ? 2u : 0u);
+}
+
+size_t ptg_accum_state_bytes(uint32_t w, uint32_t h, uint32_t flags)
+{
+    if(flags & ~(PTG_ACCUM_MOMENTS | PTG_ACCUM_FEATURES)) return 0;
+    return size_t(accum_plane_count(flags)) * w * h * sizeof(float4);
+}
+
+// A header ptg_accum_begin could have written (it may come from a file).
+static int check_accum(const char* who, const ptg_accum* acc, const void* state)
+{
+    const std::string w(who);
+    if(!acc || !state) return fail(PTG_E_INVALID, w + ": null header or state");
+    if(acc->magic != PTG_ACCUM_MAGIC || acc->version != PTG_ACCUM_VERSION)
+        return fail(PTG_E_INVALID, w + ": not a ptg_accum header (bad magic or version)");
+    if(acc->flags & ~(PTG_ACCUM_MOMENTS | PTG_ACCUM_FEATURES)) return fail(PTG_E_INVALID, w + ": unknown flag bits");
+    if(acc->sample_next < acc->sample_begin) return fail(PTG_E_INVALID, w + ": the header's sample range runs backwards");
+    return PTG_OK;
+}
+
+// The planes of a state with the header's rectangle and flags.
+static FoldPlanes accum_planes(const ptg_accum& acc, void* state)
+{
+    const size_t npix = size_t(acc.w) * acc.h;
+    FoldPlanes pl;
+    float4* next = static_cast<float4*>(state);
+    pl.acc = next;
+    next += npix;
+    if(acc.flags & PTG_ACCUM_MOMENTS)
+    {
+        pl.mom = next;
+        next += npix;
+    }
+    if(acc.flags & PTG_ACCUM_FEATURES) pl.feat = next;
+    return pl;
+}
+
+int ptg_accum_begin(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                    uint32_t flags, uint32_t sample_begin, ptg_accum* acc, void* state)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, sample_begin)) return r;
+    if(!acc || !state) return fail(PTG_E_INVALID, "ptg_accum_begin: null header or state");
+    if(flags & ~(PTG_ACCUM_MOMENTS | PTG_ACCUM_FEATURES)) return fail(PTG_E_INVALID, "ptg_accum_begin: unknown flag bits");
+    PixelMap pm;
+    if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
+    if(pm.npix) PTG_HIP(hipMemsetAsync(state, 0, ptg_accum_state_bytes(w, h, flags), ctx->stream));
+    *acc = ptg_accum{PTG_ACCUM_MAGIC, PTG_ACCUM_VERSION, *cfg, x0, y0, w, h, flags, sample_begin, sample_begin, 0u};
+    return PTG_OK;
+}
+
+int ptg_accum_add(ptg_context* ctx, ptg_accum* acc, void* state, uint32_t sample_end)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_accum("ptg_accum_add", acc, state)) return r;
+    if(sample_end <= acc->sample_next)
+        return fail(PTG_E_INVALID, "ptg_accum_add: sample_end " + std::to_string(sample_end) + " adds nothing to a state that holds samples up to " +
+                                       std::to_string(acc->sample_next));
+    const ptg_render_config cfg = acc->cfg;
+    if(int r = check_cfg(ctx, &cfg, sample_end)) return r;
+    PixelMap pm;
+    if(int r = rect_map(&cfg, acc->x0, acc->y0, acc->w, acc->h, pm)) return r;
+    if((acc->flags & PTG_ACCUM_FEATURES) && ctx->pipeline != 0)
+        return fail(PTG_E_INVALID, "ptg_accum_add: PTG_ACCUM_FEATURES runs on the wavefront pipeline only (ptg_set_pipeline(ctx, 0))");
+    const FoldPlanes planes = accum_planes(*acc, state);
+    if(int r = render_map(ctx, &cfg, pm, acc->sample_next, sample_end, nullptr, nullptr, nullptr, nullptr, nullptr, &planes))
+        return r;
+    acc->sample_next = sample_end;
+    return PTG_OK;
+}
+
+int ptg_accum_resolve(ptg_context* ctx, const ptg_accum* acc, const void* state, int by_samples, ptg_float4* out_accum,
+                      ptg_uchar4* out_bgra, ptg_float4* out_moments, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_accum("ptg_accum_resolve", acc, state)) return r;
+    if(acc->sample_next == acc->sample_begin) return fail(PTG_E_INVALID, "ptg_accum_resolve: the state holds no sample");
+    if(acc->cfg.samples_per_pixel == 0) return fail(PTG_E_INVALID, "bad render config");
+    if(out_moments && !(acc->flags & PTG_ACCUM_MOMENTS))
+        return fail(PTG_E_INVALID, "ptg_accum_resolve: out_moments of a state without PTG_ACCUM_MOMENTS");
+    if((out_albedo || out_normal_depth) && !(acc->flags & PTG_ACCUM_FEATURES))
+        return fail(PTG_E_INVALID, "ptg_accum_resolve: a feature output of a state without PTG_ACCUM_FEATURES");
+    const size_t npix = size_t(acc->w) * acc->h;
+    if(npix >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
+    const char* outs[5] = {reinterpret_cast<const char*>(out_accum), reinterpret_cast<const char*>(out_bgra),
+                           reinterpret_cast<const char*>(out_moments), reinterpret_cast<const char*>(out_albedo),
+                           reinterpret_cast<const char*>(out_normal_depth)};
+    const char* const lo = static_cast<const char*>(state);
+    const char* const hi = lo + ptg_accum_state_bytes(acc->w, acc->h, acc->flags);
+    bool any = false;
+    for(int a = 0; a < 5; ++a)
+    {
+        if(!outs[a]) continue;
+        any = true;
+        for(int b = a + 1; b < 5; ++b)
+            if(outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_accum_resolve: two outputs are the same buffer");
+        const size_t bytes = npix * (a == 1 ? sizeof(uchar4) : sizeof(float4));
+        if(outs[a] < hi && outs[a] + bytes > lo) return fail(PTG_E_INVALID, "ptg_accum_resolve: an output lies inside the state");
+    }
+    if(!any) return fail(PTG_E_INVALID, "ptg_accum_resolve: no output given");
+    if(npix == 0) return PTG_OK;
+    const FoldPlanes pl = accum_planes(*acc, const_cast<void*>(state));
+    const float div = by_samples ? (float)(acc->sample_next - acc->sample_begin) : (float)acc->cfg.samples_per_pixel;
+    return launch_plain(ctx, grid_for(npix), k_accum_resolve, uint32_t(npix), pl.acc, pl.mom, pl.feat, div,
+                        reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra),
+                        reinterpret_cast<float4*>(out_moments), reinterpret_cast<float4*>(out_albedo),
+                        reinterpret_cast<float4*>(out_normal_depth));
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

@@ -59,6 +59,76 @@ class Camera(C.Structure):
         return cls.from_buffer_copy(np.asarray(cam, dtype=CAMERA_DTYPE).tobytes())
 
 
+ACCUM_MOMENTS, ACCUM_FEATURES = 1, 2       # PTG_ACCUM_*
+ACCUM_MAGIC, ACCUM_VERSION = 0x41475450, 1  # 'PTGA'
+
+
+class Accum(C.Structure):
+    """ptg_accum: the 64-byte host header of a progressive render's state."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("cfg", RenderConfig),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32),
+                ("sample_begin", C.c_uint32), ("sample_next", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Accum) == 64
+
+
+def accum_plane_count(flags):
+    """Planes of a state with these PTG_ACCUM_* flags (ptg.h's state layout)."""
+    return 1 + (1 if flags & ACCUM_MOMENTS else 0) + (2 if flags & ACCUM_FEATURES else 0)
+
+
+def accum_pack(header: Accum, planes: np.ndarray):
+    """A checkpoint's two arrays from a header and its state's bytes (any
+    array of planes * h * w * 16 bytes): (the 16 header words, the planes as
+    uint32 [planes, h, w, 4]).  The planes are words, never floats, so a NaN's
+    payload and the sample count in the moments plane survive the file."""
+    words = np.frombuffer(bytes(header), dtype="<u4").copy()
+    shape = (accum_plane_count(header.flags), header.h, header.w, 4)
+    flat = np.ascontiguousarray(planes).reshape(-1).view(np.uint8)
+    if flat.size != 4 * int(np.prod(shape)):
+        raise ValueError("the state holds %d bytes, the header's planes %d" % (flat.size, 4 * int(np.prod(shape))))
+    return words, flat.view("<u4").reshape(shape).copy()
+
+
+def accum_unpack(words, planes):
+    """accum_pack's inverse, checked: (Accum, planes uint32 [planes, h, w, 4]).
+    ValueError on a header that is not 16 words, a wrong magic or version,
+    unknown flags, or a plane array whose shape is not the header's."""
+    words = np.asarray(words)
+    if words.shape != (16,) or words.dtype.kind != "u" or words.dtype.itemsize != 4:
+        raise ValueError("the header is 16 uint32 words, not %s %s" % (words.dtype, words.shape))
+    header = Accum.from_buffer_copy(np.ascontiguousarray(words, dtype="<u4").tobytes())
+    if header.magic != ACCUM_MAGIC:
+        raise ValueError("not an accumulator checkpoint: magic 0x%08x" % header.magic)
+    if header.version != ACCUM_VERSION:
+        raise ValueError("accumulator checkpoint version %d, this library reads %d" % (header.version, ACCUM_VERSION))
+    if header.flags & ~(ACCUM_MOMENTS | ACCUM_FEATURES):
+        raise ValueError("unknown accumulator flags 0x%x" % header.flags)
+    if header.sample_next < header.sample_begin:
+        raise ValueError("the header's sample range runs backwards")
+    planes = np.asarray(planes)
+    shape = (accum_plane_count(header.flags), header.h, header.w, 4)
+    if planes.shape != shape or planes.dtype.kind != "u" or planes.dtype.itemsize != 4:
+        raise ValueError("the planes are %s %s, the header says uint32 %s" % (planes.dtype, planes.shape, shape))
+    return header, np.ascontiguousarray(planes, dtype="<u4")
+
+
+def accum_save(path, header: Accum, planes: np.ndarray):
+    """One .npz: `header` (the 16 words) and `planes` (uint32 [planes, h, w, 4])."""
+    words, planes = accum_pack(header, planes)
+    with open(path, "wb") as f:     # an open file: np.savez appends no suffix to the name
+        np.savez(f, header=words, planes=planes)
+
+
+def accum_load(path):
+    """accum_save's file back: (Accum, planes), checked by accum_unpack."""
+    with np.load(path, allow_pickle=False) as z:
+        if "header" not in z.files or "planes" not in z.files:
+            raise ValueError("%s holds no accumulator checkpoint" % path)
+        return accum_unpack(z["header"], z["planes"])
+
+
 class Mesh(C.Structure):
     _fields_ = [("vertex_count", C.c_uint32), ("triangle_count", C.c_uint32), ("index_offset", C.c_uint32),
                 ("base_vertex_offset", C.c_uint32)]
@@ -139,6 +209,10 @@ def lib():
         "ptg_denoise": (I, [P, U32, U32, P, P, P, P, P, P]),
         "ptg_render_moments": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P]),
         "ptg_render_with_features": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P, P, P]),
+        "ptg_accum_state_bytes": (SZ, [U32, U32, U32]),
+        "ptg_accum_begin": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P]),
+        "ptg_accum_add": (I, [P, P, P, U32]),
+        "ptg_accum_resolve": (I, [P, P, P, I, P, P, P, P, P]),
         "ptg_denoise_guided_params_default": (None, [P]),
         "ptg_denoise_guided": (I, [P, U32, U32, P, P, P, P, P, P, P]),
         "ptg_temporal_params_default": (None, [P]),

@@ -296,6 +296,18 @@ class GpuRenderer:
         out, bgra = self.denoise_guided(acc, albedo, normal_depth, moments, guided_params, want_bgra=True, out_radiance=acc)
         return bgra, out
 
+    # -- progressive rendering -------------------------------------------------
+    def render_progressive(self, cfg: N.RenderConfig, steps, rect=None, moments=True, features=True, sample_begin=0):
+        """A generator over one ``Accumulator``: for each sample end of the
+        increasing list `steps` it adds the samples up to there and yields
+        (samples_done, accumulator); ``accumulator.resolve()`` then gives the
+        image so far, and after the last step the bits of the one-shot
+        render.  The caller may stop iterating at any step."""
+        acc = Accumulator(self, cfg, rect=rect, moments=moments, features=features, sample_begin=sample_begin)
+        for end in steps:
+            acc.add(end)
+            yield acc.samples_done, acc
+
     # -- temporal accumulation -------------------------------------------------
     def _temporal(self, entry, p, cams, radiance, moments, albedo, normal_depth, history, want_bgra, out_radiance,
                   out_moments, flags=()):
@@ -484,6 +496,102 @@ class GpuRenderer:
             self.close()
         except Exception:
             pass
+
+
+class Accumulator:
+    """A resumable render of one frame (ptg_accum_*): the running per-pixel
+    sums as a tensor this object owns, ``state`` (float32 [planes, h, w, 4]
+    on the renderer's GPU, ptg.h's state layout: the radiance sums, then with
+    `moments` the plane (s1, s2, n as bits, 0), then with `features` the
+    albedo + coverage and the normal + depth sums).
+
+    ``add(sample_end)`` traces the samples up to `sample_end` into it,
+    ``resolve()`` gives the image of the samples so far and leaves the state
+    alone, ``save`` / ``load`` keep it in a file.  However the samples are
+    split into adds, and through a save and a load into another renderer or
+    process, ``resolve()`` gives the bits of
+    ``render_with_features(cfg, rect, (sample_begin, samples_done))``.  The
+    renderer must have the same scene and frame uploaded at every add: that
+    is the caller's contract, nothing checks it."""
+
+    def __init__(self, renderer: GpuRenderer, cfg: N.RenderConfig, rect=None, moments=True, features=True, sample_begin=0,
+                 _restore=None):
+        import torch
+        self.renderer = renderer
+        dev = torch.device("cuda", renderer.device)
+        if _restore is not None:            # Accumulator.load: the header and the planes of a checkpoint
+            self.header, planes = _restore
+            self.state = torch.from_numpy(planes.view(np.float32)).to(dev)
+            return
+        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+        flags = (N.ACCUM_MOMENTS if moments else 0) | (N.ACCUM_FEATURES if features else 0)
+        self.header = N.Accum()
+        self.state = torch.empty((N.accum_plane_count(flags), h, w, 4), dtype=torch.float32, device=dev)
+        N.check(N.lib().ptg_accum_begin(renderer._ctx, C.byref(cfg), x0, y0, w, h, flags, sample_begin,
+                                        C.byref(self.header), _ptr(self.state)), "ptg_accum_begin")
+
+    @property
+    def cfg(self):
+        return self.header.cfg
+
+    @property
+    def rect(self):
+        return (self.header.x0, self.header.y0, self.header.w, self.header.h)
+
+    @property
+    def moments(self):
+        return bool(self.header.flags & N.ACCUM_MOMENTS)
+
+    @property
+    def features(self):
+        return bool(self.header.flags & N.ACCUM_FEATURES)
+
+    @property
+    def sample_begin(self):
+        return self.header.sample_begin
+
+    @property
+    def samples_done(self):
+        """The sample index the state has reached: it holds [sample_begin, samples_done)."""
+        return self.header.sample_next
+
+    def add(self, sample_end):
+        """Trace samples [samples_done, sample_end) into the state (ptg_accum_add).  Asynchronous."""
+        N.check(N.lib().ptg_accum_add(self.renderer._ctx, C.byref(self.header), _ptr(self.state), int(sample_end)),
+                "ptg_accum_add")
+        return self
+
+    def resolve(self, by_samples=False):
+        """(bgra, accum, moments, albedo+coverage, normal+depth) of the samples
+        so far, the order of render_with_features, with None for what the
+        flags exclude.  by_samples=False divides by cfg.samples_per_pixel (the
+        bits of the one-shot render of the same sample range), by_samples=True
+        by the samples taken (a preview at the final brightness).  The state
+        is not changed.  Asynchronous."""
+        import torch
+        _, _, w, h = self.rect
+        dev = self.state.device
+        new = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        accum = new()
+        moments = new() if self.moments else None
+        albedo, normal_depth = (new(), new()) if self.features else (None, None)
+        N.check(N.lib().ptg_accum_resolve(self.renderer._ctx, C.byref(self.header), _ptr(self.state), 1 if by_samples else 0,
+                                          _ptr(accum), _ptr(bgra), _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
+                "ptg_accum_resolve")
+        return bgra, accum, moments, albedo, normal_depth
+
+    def save(self, path):
+        """The checkpoint: one .npz with the 16 header words and the planes as
+        uint32 [planes, h, w, 4] (native.accum_save).  Waits for the adds queued so far."""
+        self.renderer.synchronize()
+        N.accum_save(path, self.header, self.state.cpu().numpy())
+
+    @classmethod
+    def load(cls, renderer: GpuRenderer, path):
+        """An accumulator on `renderer` continuing save's file; ValueError on
+        a file that is no checkpoint (native.accum_unpack)."""
+        return cls(renderer, None, _restore=N.accum_load(path))
 
 
 class TemporalDenoiser:
