@@ -364,13 +364,77 @@ int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg,
  * rays, so no second walk is made; under ptg_set_pipeline(ctx, 1) the two
  * passes run one after the other.  A null feature output, or two outputs
  * that are the same buffer, is PTG_E_INVALID; rectangle, sample range and
- * configuration are checked as ptg_render checks them.  A rectangle only (no
- * tile set).  DEVICE pointers; asynchronous on the context's stream. */
+ * configuration are checked as ptg_render checks them.  A rectangle only (the
+ * tile set is ptg_render_tiles_packed).  DEVICE pointers; asynchronous on the
+ * context's stream. */
 int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg,
                              uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                              uint32_t sample_begin, uint32_t sample_end,
                              ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments,
                              ptg_float4* out_albedo, ptg_float4* out_normal_depth);
+
+/* ---- tile packs: the five planes of a tile shard in one buffer ----------
+ *
+ * A tile pack is what one rank of a tile shard sends to the rank that
+ * assembles the frame: ptg_render_with_features' five planes of its tiles in
+ * ONE contiguous DEVICE buffer, so that one gather ships them all.  For
+ * pack_tiles tiles of tile_w x tile_h pixels, S = pack_tiles * tile_w * tile_h
+ * slots and the planes start at these byte offsets of the pack:
+ *
+ *     accum         0       [S] ptg_float4
+ *     moments       16 * S  [S] ptg_float4
+ *     albedo        32 * S  [S] ptg_float4
+ *     normal_depth  48 * S  [S] ptg_float4
+ *     bgra          64 * S  [S] ptg_uchar4
+ *
+ * Slot k * tile_w * tile_h + q of every plane holds pixel q (row-major within
+ * the tile) of the rank's k-th tile: ptg_render_tiles' slot order.
+ *
+ * ptg_tile_pack_bytes is the pack's size: 68 * S rounded up to a multiple of
+ * 256, which is also the stride from one rank's pack to the next in a
+ * gathered buffer.  68 * S alone need not be a multiple of 16 (one 5 x 3 tile:
+ * 1020), and the float4 planes of the second pack would then be misaligned.
+ * 0 for a zero dimension, or when S does not stay below 2^31. */
+size_t ptg_tile_pack_bytes(uint32_t tile_w, uint32_t tile_h, uint32_t pack_tiles);
+
+/* ptg_render_with_features over ptg_render_tiles' tile set and the whole
+ * sample range [0, cfg->samples_per_pixel), written into a tile pack sized
+ * for pack_tiles >= tile_count tiles (every rank of a shard sizes its pack
+ * for the largest tile count, so that the packs gather).  Every plane value
+ * of a pixel inside the image is the bit pattern ptg_render_with_features
+ * writes for that pixel in a render of the full rectangle; no arithmetic of
+ * its own is defined.  Every other byte of the pack - pixels outside the
+ * image, the tiles from tile_count to pack_tiles, the padding - is 0: the
+ * pack is cleared on the stream before the render.  Under
+ * ptg_set_pipeline(ctx, 1) the two passes run one after the other, as in
+ * ptg_render_with_features.  pack_tiles < tile_count, a null pack or one that
+ * is not 16-byte aligned is PTG_E_INVALID; the tile set and the configuration
+ * are checked as ptg_render_tiles checks them.  A refused call launches
+ * nothing.  Asynchronous on the context's stream. */
+int ptg_render_tiles_packed(ptg_context* ctx, const ptg_render_config* cfg,
+                            uint32_t tile_w, uint32_t tile_h,
+                            uint32_t first_tile, uint32_t tile_stride, uint32_t tile_count,
+                            uint32_t pack_tiles, void* pack /* DEVICE, ptg_tile_pack_bytes */);
+
+/* The frame from the gathered packs of a `world`-rank tile shard: tile t
+ * (row-major over the image) was rendered by rank t % world as its tile
+ * t / world (first_tile = rank, tile_stride = world), and pack r starts at
+ * packs + r * ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles).  ONE launch
+ * copies every requested plane of the whole image: a work-item owns an image
+ * pixel, finds its pack and slot, loads the pixel's value from each requested
+ * plane and stores it at out_*[y * width + x] (each output optional,
+ * [height][width]).  Every pixel has exactly one source, so the outputs need
+ * no clearing, and the values are the packs' bits.  No output, two outputs
+ * that are the same buffer, an output that overlaps `packs`, world == 0, a
+ * null `packs` or a pointer that is not aligned for its elements (16 bytes;
+ * out_bgra 4) is PTG_E_INVALID; pack_tiles below ceil(tiles / world) is
+ * PTG_E_RANGE.  A refused call launches nothing.  Needs no scene.  DEVICE
+ * pointers; asynchronous on the context's stream. */
+int ptg_assemble_tile_packs(ptg_context* ctx, const ptg_render_config* cfg,
+                            uint32_t tile_w, uint32_t tile_h, uint32_t world, uint32_t pack_tiles,
+                            const void* packs /* world packs back to back */,
+                            ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments,
+                            ptg_float4* out_albedo, ptg_float4* out_normal_depth);
 
 /* ptg_denoise with the luminance range set per pixel by the variance of the
  * pixel's mean (moments.z of ptg_render_moments) instead of a fixed

@@ -16,7 +16,9 @@
 //   k_rays          ray_query closest hit + shadow any-hit (parity)
 //   k_camera_rays   camera_ray's first ray per (pixel, sample) (parity)
 //   k_scatter_tiles
-//   k_features      first-hit albedo, normal and depth
+//   k_assemble_tile_packs  a frame's five planes from a tile shard's gathered
+//                   packs in one launch (ptg_assemble_tile_packs)
+//   k_features     first-hit albedo, normal and depth
 //   k_fold_features the same sums from the features round 0 of a fused render
 //                   stored per sample (ptg_render_with_features: k_wf_shade /
 //                   k_wf_sky with FEAT), folded beside k_accumulate
@@ -901,6 +903,40 @@ __global__ void k_scatter_tiles(PixelMap pm, const uchar4* __restrict__ tiles, u
     if(p >= pm.npix) return;
     uint32_t x, y;
     if(pm.pixel(p, x, y)) image[size_t(y) * pm.img_w + x] = tiles[p];
+}
+
+// The frame from the gathered tile packs of a `world`-rank shard (ptg.h, tile
+// packs), in gather form: one work-item per image pixel, so consecutive lanes
+// store consecutive addresses of every output and load runs of tw consecutive
+// slots.  Tile t = rank t % world's tile t / world; the pixel's slot is the
+// same in all five planes of that rank's pack.  Pure copies: 16-byte loads
+// (4 for the bytes), non-temporal since every slot is read once.  The host
+// checked that pack_tiles covers every rank's tiles, so slot < slots.
+struct AssembleOut {
+    float4 *accum, *moments, *albedo, *normal_depth;   // each may be null
+    uint32_t* bgra;                                    // a uchar4 pixel as one word
+};
+
+__global__ __launch_bounds__(kBlock) void k_assemble_tile_packs(uint32_t img_w, uint32_t npix, uint32_t tw, uint32_t th,
+                                                                uint32_t tiles_x, uint32_t world, uint32_t slots,
+                                                                size_t pack_bytes, const uint8_t* __restrict__ packs,
+                                                                AssembleOut out)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= npix) return;
+    const uint32_t x = p % img_w, y = p / img_w;
+    const uint32_t tx = x / tw, ty = y / th;
+    const uint32_t t = ty * tiles_x + tx;
+    const uint32_t rank = t % world, k = t / world;
+    const uint32_t slot = k * (tw * th) + (y - ty * th) * tw + (x - tx * tw);
+    const uint8_t* pack = packs + size_t(rank) * pack_bytes;
+    const float4* planes = reinterpret_cast<const float4*>(pack);
+    if(out.accum) out.accum[p] = nt_load(planes + slot);
+    if(out.moments) out.moments[p] = nt_load(planes + size_t(slots) + slot);
+    if(out.albedo) out.albedo[p] = nt_load(planes + 2 * size_t(slots) + slot);
+    if(out.normal_depth) out.normal_depth[p] = nt_load(planes + 3 * size_t(slots) + slot);
+    if(out.bgra)
+        out.bgra[p] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(pack + 64 * size_t(slots)) + slot);
 }
 
 // ---- first-hit feature buffers (the a-trous denoiser over them: image_ops.hip) ----
@@ -2302,6 +2338,20 @@ int ptg_camera_rays(ptg_context* ctx, const ptg_render_config* cfg, size_t n, co
     return PTG_OK;
 }
 
+// The feature pass over the pixels of `pm` (a rectangle or a tile set), its arguments checked.
+static int features_map(ptg_context* ctx, const ptg_render_config* cfg, const PixelMap& pm, uint32_t sample_begin,
+                        uint32_t sample_end, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
+{
+    // persistent blocks, each taking groups of kBlock / 8 pixels (4 waves of 8
+    // pixels x 8 samples); every walk lane owns stack_bound entries of spill
+    const uint32_t grid = std::min<uint32_t>(grid_for(pm.npix, kBlock / 8), std::max(1u, ctx->persistent_blocks / 4u));   // 8 per CU
+    PTG_HIP(ctx->grow(ctx->feat_spill, std::max<size_t>(1, size_t(grid) * kBlock * ctx->stack_bound) * sizeof(uint2)));
+    DevScene sc = ctx->scene_args(cfg);
+    sc.spill = ctx->feat_spill.as<uint2>();
+    return launch_plain(ctx, grid, k_features, sc, pm, sample_begin, sample_end, (float)cfg->samples_per_pixel,
+                        reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth));
+}
+
 int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                         uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
 {
@@ -2312,14 +2362,7 @@ int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t
     if(pm.npix == 0) return PTG_OK;
     if(!out_albedo || !out_normal_depth) return fail(PTG_E_INVALID, "ptg_render_features: null output");
     if(sample_end <= sample_begin) return fail(PTG_E_INVALID, "empty sample range");
-    // persistent blocks, each taking groups of kBlock / 8 pixels (4 waves of 8
-    // pixels x 8 samples); every walk lane owns stack_bound entries of spill
-    const uint32_t grid = std::min<uint32_t>(grid_for(pm.npix, kBlock / 8), std::max(1u, ctx->persistent_blocks / 4u));   // 8 per CU
-    PTG_HIP(ctx->grow(ctx->feat_spill, std::max<size_t>(1, size_t(grid) * kBlock * ctx->stack_bound) * sizeof(uint2)));
-    DevScene sc = ctx->scene_args(cfg);
-    sc.spill = ctx->feat_spill.as<uint2>();
-    return launch_plain(ctx, grid, k_features, sc, pm, sample_begin, sample_end, (float)cfg->samples_per_pixel,
-                        reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth));
+    return features_map(ctx, cfg, pm, sample_begin, sample_end, out_albedo, out_normal_depth);
 }
 
 int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -2343,6 +2386,98 @@ int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uin
         return ptg_render_features(ctx, cfg, x0, y0, w, h, sample_begin, sample_end, out_albedo, out_normal_depth);
     }
     return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments, out_albedo, out_normal_depth);
+}
+
+// ---- tile packs: a tile shard's five planes in one buffer (ptg.h) ----
+
+// The slots of a pack, 0 when a dimension is 0 or they do not stay below 2^31.
+static uint64_t tile_pack_slots(uint32_t tw, uint32_t th, uint32_t pack_tiles)
+{
+    const uint64_t per = uint64_t(tw) * th;
+    if(per == 0 || pack_tiles == 0 || per >= (1ull << 31)) return 0;
+    const uint64_t slots = per * pack_tiles;   // below 2^63
+    return slots < (1ull << 31) ? slots : 0;
+}
+
+size_t ptg_tile_pack_bytes(uint32_t tile_w, uint32_t tile_h, uint32_t pack_tiles)
+{
+    const uint64_t slots = tile_pack_slots(tile_w, tile_h, pack_tiles);
+    return size_t((slots * (4 * sizeof(float4) + sizeof(uchar4)) + 255u) & ~uint64_t(255));
+}
+
+int ptg_render_tiles_packed(ptg_context* ctx, const ptg_render_config* cfg, uint32_t tile_w, uint32_t tile_h,
+                            uint32_t first_tile, uint32_t tile_stride, uint32_t tile_count, uint32_t pack_tiles, void* pack)
+{
+    if(int r = bind(ctx)) return r;
+    if(int r = check_cfg(ctx, cfg, cfg ? cfg->samples_per_pixel : 0)) return r;
+    if(pack_tiles < tile_count)
+        return fail(PTG_E_INVALID, "ptg_render_tiles_packed: a pack of " + std::to_string(pack_tiles) + " tiles for " +
+                                       std::to_string(tile_count));
+    if(!pack) return fail(PTG_E_INVALID, "ptg_render_tiles_packed: null pack");
+    if(reinterpret_cast<uintptr_t>(pack) % sizeof(float4)) return fail(PTG_E_INVALID, "ptg_render_tiles_packed: the pack is not 16-byte aligned");
+    PixelMap pm;
+    if(int r = tile_map(cfg, tile_w, tile_h, first_tile, tile_stride, tile_count, pm)) return r;
+    if(pack_tiles == 0) return PTG_OK;   // no tile and no byte
+    const uint64_t slots = tile_pack_slots(tile_w, tile_h, pack_tiles);
+    if(slots == 0) return fail(PTG_E_RANGE, "ptg_render_tiles_packed: too many pack slots");
+    // everything the render does not write - pixels outside the image in the
+    // feature planes, the tiles behind tile_count, the padding - is 0
+    PTG_HIP(hipMemsetAsync(pack, 0, ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles), ctx->stream));
+    if(pm.npix == 0) return PTG_OK;
+    ptg_float4* planes = static_cast<ptg_float4*>(pack);
+    ptg_float4 *accum = planes, *moments = planes + slots, *albedo = planes + 2 * slots, *normal_depth = planes + 3 * slots;
+    ptg_uchar4* bgra = reinterpret_cast<ptg_uchar4*>(planes + 4 * slots);
+    const uint32_t spp = cfg->samples_per_pixel;
+    if(ctx->pipeline != 0)
+    {   // as ptg_render_with_features: the two passes, one after the other
+        if(int r = render_map(ctx, cfg, pm, 0, spp, accum, bgra, moments)) return r;
+        return features_map(ctx, cfg, pm, 0, spp, albedo, normal_depth);
+    }
+    return render_map(ctx, cfg, pm, 0, spp, accum, bgra, moments, albedo, normal_depth);
+}
+
+int ptg_assemble_tile_packs(ptg_context* ctx, const ptg_render_config* cfg, uint32_t tile_w, uint32_t tile_h, uint32_t world,
+                            uint32_t pack_tiles, const void* packs, ptg_float4* out_accum, ptg_uchar4* out_bgra,
+                            ptg_float4* out_moments, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
+{
+    if(int r = bind(ctx)) return r;
+    if(!cfg || cfg->width == 0 || cfg->height == 0) return fail(PTG_E_INVALID, "bad render config");
+    const uint64_t npix = uint64_t(cfg->width) * cfg->height;
+    if(npix >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
+    if(tile_w == 0 || tile_h == 0) return fail(PTG_E_INVALID, "bad tile geometry");
+    if(world == 0) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: world size 0");
+    if(!packs) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: null packs");
+    if(reinterpret_cast<uintptr_t>(packs) % sizeof(float4)) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: the packs are not 16-byte aligned");
+    const uint32_t tiles_x = (cfg->width + tile_w - 1) / tile_w, tiles_y = (cfg->height + tile_h - 1) / tile_h;
+    const uint64_t need = (uint64_t(tiles_x) * tiles_y + world - 1) / world;
+    if(pack_tiles < need)
+        return fail(PTG_E_RANGE, "ptg_assemble_tile_packs: packs of " + std::to_string(pack_tiles) + " tiles, the largest rank holds " +
+                                     std::to_string(need));
+    const uint64_t slots = tile_pack_slots(tile_w, tile_h, pack_tiles);
+    if(slots == 0) return fail(PTG_E_RANGE, "ptg_assemble_tile_packs: too many pack slots");
+    const size_t pack_bytes = ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles);
+    const char* outs[5] = {reinterpret_cast<const char*>(out_accum), reinterpret_cast<const char*>(out_bgra),
+                           reinterpret_cast<const char*>(out_moments), reinterpret_cast<const char*>(out_albedo),
+                           reinterpret_cast<const char*>(out_normal_depth)};
+    const char* const lo = static_cast<const char*>(packs);
+    const char* const hi = lo + size_t(world) * pack_bytes;
+    bool any = false;
+    for(int a = 0; a < 5; ++a)
+    {
+        if(!outs[a]) continue;
+        any = true;
+        const size_t elem = a == 1 ? sizeof(uchar4) : sizeof(float4);
+        if(reinterpret_cast<uintptr_t>(outs[a]) % elem) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: a misaligned output");
+        for(int b = a + 1; b < 5; ++b)
+            if(outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: two outputs are the same buffer");
+        if(outs[a] < hi && outs[a] + npix * elem > lo) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: an output overlaps the packs");
+    }
+    if(!any) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: no output given");
+    const AssembleOut out{reinterpret_cast<float4*>(out_accum), reinterpret_cast<float4*>(out_moments),
+                          reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth),
+                          reinterpret_cast<uint32_t*>(out_bgra)};
+    return launch_plain(ctx, grid_for(npix), k_assemble_tile_packs, cfg->width, uint32_t(npix), tile_w, tile_h, tiles_x, world,
+                        uint32_t(slots), pack_bytes, static_cast<const uint8_t*>(packs), out);
 }
 
 // ---- progressive rendering (ptg_accum_*) ----

@@ -22,6 +22,11 @@ partitioned, never exchanged, except for one real step:
             the uchar4 tiles to rank 0 over xGMI assembles the framebuffer
             (3.7 MB at 720p: each peer sends ~0.46 MB over its own link, a
             point-to-point shape - no ring all-reduce).
+            `render_and_gather_planes` is the same shard for all five planes
+            of render_with_features (radiance, moments, albedo, normal+depth,
+            BGRA: one tile pack per rank, 68 bytes per pixel, still ONE
+            gather, one assembling launch on rank 0), and
+            `render_and_denoise` filters the assembled frame there.
 
 Per-pixel results do not depend on the partition: every pixel's samples are
 summed in index order on one GPU, so a sharded frame is bit-identical to a
@@ -103,6 +108,49 @@ def assemble_numpy(shard: TileShard, gathered, image):
     return image
 
 
+PACK_PLANES = ("accum", "moments", "albedo", "normal_depth", "bgra")   # a tile pack's planes, in pack order
+
+
+def tile_pack_layout(shard: TileShard):
+    """The tile pack of `shard` (include/ptg.h, tile packs), sized for the
+    largest tile count among its ranks so that the ranks' packs gather:
+    {"pack_tiles", "slots", the byte offset of each plane of PACK_PLANES,
+    "bytes"}.  "bytes" is ptg_tile_pack_bytes: 68 bytes per slot rounded up to
+    a multiple of 256, also the stride between the packs of a gathered
+    buffer."""
+    pack_tiles = shard.max_count
+    slots = pack_tiles * shard.tile_w * shard.tile_h
+    if shard.tile_w <= 0 or shard.tile_h <= 0 or slots >= 1 << 31:
+        slots = 0
+    lay = {"pack_tiles": pack_tiles, "slots": slots}
+    lay.update({name: 16 * k * slots for k, name in enumerate(PACK_PLANES)})
+    lay["bytes"] = (68 * slots + 255) // 256 * 256
+    return lay
+
+
+def assemble_packs_numpy(shard: TileShard, packs):
+    """CPU twin of ptg_assemble_tile_packs: the frame from the gathered packs
+    of `shard`'s ranks (uint8, world x tile_pack_layout(shard)["bytes"]), in
+    the kernel's gather form - every image pixel looks up its rank, tile and
+    slot.  Returns (bgra uint8, accum, moments, albedo, normal_depth float32),
+    each [H, W, 4] and a copy of the packs' bits."""
+    lay = tile_pack_layout(shard)
+    packs = np.ascontiguousarray(packs, dtype=np.uint8).reshape(shard.world, lay["bytes"])
+    y, x = np.mgrid[0:shard.height, 0:shard.width]
+    ty, tx = y // shard.tile_h, x // shard.tile_w
+    t = ty * shard.tiles_x + tx
+    rank, k = t % shard.world, t // shard.world
+    slot = k * (shard.tile_w * shard.tile_h) + (y - ty * shard.tile_h) * shard.tile_w + (x - tx * shard.tile_w)
+    s = lay["slots"]
+    out = {}
+    for name in PACK_PLANES:
+        words = 1 if name == "bgra" else 4
+        plane = packs[:, lay[name]:lay[name] + 4 * words * s].view("<u4").reshape(shard.world, s, words)
+        px = np.ascontiguousarray(plane[rank, slot])                      # [H, W, words] uint32: bits, never floats
+        out[name] = px.view(np.uint8) if name == "bgra" else px.view(np.float32)
+    return out["bgra"], out["accum"], out["moments"], out["albedo"], out["normal_depth"]
+
+
 class ShardMismatch(RuntimeError):
     """The ranks of one collective render disagree on its shape (raised on every rank)."""
 
@@ -139,7 +187,7 @@ def _agree(kind, cfg, a, b, shard_rank, shard_world, group_ok, dev, what):
     keys = [tuple(rec[:10]) for rec in recs]
     if any(k != keys[0] for k in keys):
         names = list(_FIELDS)
-        names[7:9] = ("tile_w", "tile_h") if kind == 1 else ("image_h", "image_w")
+        names[7:9] = ("tile_w", "tile_h") if kind in (1, 3) else ("image_h", "image_w")
         diff = [i for i in range(10) if len({k[i] for k in keys}) > 1]
         raise ShardMismatch("%s: the ranks disagree on %s (%s)" % (what, ", ".join(names[i] for i in diff), "; ".join(
             "rank %d: %s" % (r, {names[i]: rec[i] for i in diff}) for r, rec in enumerate(recs))))
@@ -230,6 +278,82 @@ def render_and_gather(renderer, cfg, shard: TileShard, image, stream=None, force
                 if n:
                     renderer.scatter_tiles(cfg, shard.tile_w, shard.tile_h, r, shard.world, n, part, image)
     return image
+
+
+def _renderer_device(renderer):
+    """The torch device a renderer's tensors live on: GpuRenderer.device is a
+    GPU ordinal; an object without one (a CPU stand-in) works in host memory."""
+    import torch
+    d = getattr(renderer, "device", "cpu")
+    return torch.device("cuda", d) if isinstance(d, int) else torch.device(d)
+
+
+def render_and_gather_planes(renderer, cfg, shard: TileShard, stream=None, force_collective=True):
+    """render_and_gather for all five planes of render_with_features: render
+    this rank's tiles into one tile pack (renderer.render_tiles_packed), gather
+    the packs to rank 0 in ONE collective and assemble the frame there in one
+    launch (renderer.assemble_tile_packs).  Rank 0 returns (bgra, accum,
+    moments, albedo+coverage, normal+depth), the bits of
+    render_with_features(cfg) on one GPU; the other ranks return None.
+
+    Streams, the one-rank cases, `force_collective` and gloo's path through
+    host memory are render_and_gather's.  The ranks agree on the call first
+    under a kind of its own, so a rank that calls render_and_gather while the
+    others call this function makes EVERY rank raise ShardMismatch."""
+    import contextlib
+
+    import torch
+    import torch.distributed as dist
+    dev = _renderer_device(renderer)
+    lay = tile_pack_layout(shard)
+    agree, collective = _collective_mode(shard, force_collective, "render_and_gather_planes")
+    ctx = torch.cuda.stream(stream) if (stream is not None and dev.type == "cuda") else contextlib.nullcontext()
+    with ctx:
+        if agree:
+            _agree(3, cfg, shard.tile_w, shard.tile_h, shard.rank, shard.world, _place_ok(shard), dev,
+                   "render_and_gather_planes")
+        # a rank without a tile still clears and sends its pack
+        pack = renderer.render_tiles_packed(cfg, shard.tile_w, shard.tile_h, shard.first, shard.stride, shard.count,
+                                            lay["pack_tiles"])
+        if not collective:
+            packs = pack.view(1, -1)
+        elif dist.get_backend() == "gloo":   # CPU process groups: gather through host memory
+            host = pack.cpu()
+            hparts = [torch.empty_like(host) for _ in range(shard.world)] if shard.rank == 0 else None
+            dist.gather(host, hparts, dst=0)
+            packs = torch.stack(hparts).to(dev) if shard.rank == 0 else None
+        else:                                # RCCL over xGMI: one gather of the uint8 packs to rank 0
+            packs = torch.empty((shard.world, lay["bytes"]), dtype=torch.uint8, device=dev) if shard.rank == 0 else None
+            dist.gather(pack, list(packs.unbind(0)) if shard.rank == 0 else None, dst=0)
+        if shard.rank != 0:
+            return None
+        return renderer.assemble_tile_packs(cfg, shard.tile_w, shard.tile_h, shard.world, lay["pack_tiles"], packs)
+
+
+def render_and_denoise(renderer, cfg, shard: TileShard, params=None, stream=None, force_collective=True):
+    """A denoised frame from a tile shard: render_and_gather_planes, then the
+    à-trous filter over the assembled images on rank 0 (the filter costs a
+    thousandth of the render, so it is not sharded) - renderer.denoise_guided
+    with `params` a denoise.DenoiseGuidedParams (default: its default()), or
+    renderer.denoise when `params` is a denoise.DenoiseParams.  Rank 0 returns
+    (bgra, denoised radiance), the bits of GpuRenderer.render_denoised_guided
+    / render_denoised of the same frame on one GPU; the other ranks return
+    None."""
+    import contextlib
+
+    import torch
+    from .denoise import DenoiseParams
+    planes = render_and_gather_planes(renderer, cfg, shard, stream=stream, force_collective=force_collective)
+    if planes is None:
+        return None
+    _, acc, moments, albedo, normal_depth = planes
+    ctx = torch.cuda.stream(stream) if (stream is not None and acc.device.type == "cuda") else contextlib.nullcontext()
+    with ctx:
+        if isinstance(params, DenoiseParams):
+            out, bgra = renderer.denoise(acc, albedo, normal_depth, params, want_bgra=True, out_radiance=acc)
+        else:
+            out, bgra = renderer.denoise_guided(acc, albedo, normal_depth, moments, params, want_bgra=True, out_radiance=acc)
+    return bgra, out
 
 
 @dataclass

@@ -209,6 +209,9 @@ def lib():
         "ptg_denoise": (I, [P, U32, U32, P, P, P, P, P, P]),
         "ptg_render_moments": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P]),
         "ptg_render_with_features": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P, P, P]),
+        "ptg_tile_pack_bytes": (SZ, [U32, U32, U32]),
+        "ptg_render_tiles_packed": (I, [P, P, U32, U32, U32, U32, U32, U32, P]),
+        "ptg_assemble_tile_packs": (I, [P, P, U32, U32, U32, U32, P, P, P, P, P, P]),
         "ptg_accum_state_bytes": (SZ, [U32, U32, U32]),
         "ptg_accum_begin": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P]),
         "ptg_accum_add": (I, [P, P, P, U32]),

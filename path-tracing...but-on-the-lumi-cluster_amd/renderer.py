@@ -114,6 +114,40 @@ class GpuRenderer:
         N.check(N.lib().ptg_scatter_tiles(self._ctx, C.byref(cfg), tile_w, tile_h, first, stride, count,
                                           _ptr(tiles_bgra), _ptr(image_bgra)), "ptg_scatter_tiles")
 
+    def render_tiles_packed(self, cfg: N.RenderConfig, tile_w, tile_h, first, stride, count, pack_tiles, out=None):
+        """render_with_features over an interleaved tile set, all five planes
+        in one tile pack sized for `pack_tiles` tiles (ptg_render_tiles_packed;
+        distributed.tile_pack_layout names the planes' offsets): a uint8
+        device tensor of ptg_tile_pack_bytes bytes, every byte that is no
+        image pixel 0.  `out` may be such a tensor (one row of a gathered
+        buffer).  Asynchronous."""
+        import torch
+        nbytes = N.lib().ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles)
+        if out is None:
+            out = torch.empty((nbytes,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        assert out.dtype == torch.uint8 and out.numel() == nbytes and out.is_contiguous()
+        N.check(N.lib().ptg_render_tiles_packed(self._ctx, C.byref(cfg), tile_w, tile_h, first, stride, count, pack_tiles,
+                                                _ptr(out)), "ptg_render_tiles_packed")
+        return out
+
+    def assemble_tile_packs(self, cfg: N.RenderConfig, tile_w, tile_h, world, pack_tiles, packs):
+        """The frame from the gathered packs of a `world`-rank tile shard
+        (`packs`: a contiguous uint8 device tensor, world packs back to back)
+        in one launch (ptg_assemble_tile_packs): (bgra, accum, moments,
+        albedo+coverage, normal+depth), render_with_features' order and
+        shapes.  Asynchronous."""
+        import torch
+        assert packs.dtype == torch.uint8 and packs.is_contiguous()
+        assert packs.numel() == world * N.lib().ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles)
+        h, w = cfg.height, cfg.width
+        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=packs.device)
+        accum, moments, albedo, normal_depth = (torch.empty((h, w, 4), dtype=torch.float32, device=packs.device)
+                                                for _ in range(4))
+        N.check(N.lib().ptg_assemble_tile_packs(self._ctx, C.byref(cfg), tile_w, tile_h, world, pack_tiles, _ptr(packs),
+                                                _ptr(accum), _ptr(bgra), _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
+                "ptg_assemble_tile_packs")
+        return bgra, accum, moments, albedo, normal_depth
+
     # -- per-sample / per-ray entry points (parity) -------------------------
     def path_trace_samples(self, cfg, xy: np.ndarray, sample_index: np.ndarray) -> np.ndarray:
         xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
