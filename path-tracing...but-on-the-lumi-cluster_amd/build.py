@@ -62,8 +62,18 @@ def build_oracle(verbose=False, jobs=8, with_reference=None):
 
 def build_test_kernels(verbose=False):
     """The user-kernel library of tests/test_gpu_device_dropin.py: a HIP kernel
-    built against include/ptg_device.h alone (test infrastructure)."""
+    built against include/ptg_device.h alone (test infrastructure); and the math
+    probe library of tests/test_gpu_math_probe.py: the rounding certificates and
+    the glibc restatement behind C entry points, with their host-libm reference.
+    The probe library belongs to the tests beside it: where tests/ is an older
+    suite without tests/math_probe (run against this build), nothing uses it,
+    and the rest of the build must not stop there."""
     _run(["make"], os.path.join(ROOT, "tests", "device_dropin"), verbose)
+    probe = os.path.join(ROOT, "tests", "math_probe")
+    if os.path.exists(os.path.join(probe, "Makefile")):
+        _run(["make"], probe, verbose)
+    elif verbose:
+        print("tests/math_probe is not in this tree: the probe library is not built", flush=True)
 
 
 def build_tools(verbose=False):

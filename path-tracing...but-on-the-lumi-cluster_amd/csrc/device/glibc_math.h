@@ -10,7 +10,9 @@
 // and a 1-ulp double difference can change the float a sum or product rounds
 // to.  So the hot path calls these restatements instead, and
 // tools/exhaustive_f64.hip proves them equal to glibc bit for bit on every
-// float argument.
+// float argument (by hand, minutes); tests/test_gpu_math_probe.py pins them
+// with the suite on every 4099th float, around each branch threshold below
+// and on doubles that are not floats (tests/math_probe/, tests/math_inputs.py).
 //
 // What is restated: glibc 2.35 (Ubuntu 2.35-0ubuntu3.11, the libm the
 // reference and the oracle link here and on the GPU boxes), whose exp and pow

@@ -187,6 +187,11 @@ PTG_D float fexp(float x) { return (float)exp((double)x); }
 //    range, 30..54 in its subnormal range, where the quantum is 2^-149).
 //    Across a binade edge v sits next to a float, not a midpoint.  NaN: no
 //    certificate.
+//  * tests/test_gpu_math_probe.py (tests/math_probe/) calls float_certain and
+//    every wrapper directly: float_certain against an integer model at every
+//    exponent, margin and edge; each wrapper against the host's libm on the
+//    path's domain, on arguments whose double is next to a float midpoint
+//    (tests/golden/cert_midpoints.npz), and at its preconditions' edges.
 constexpr uint32_t kMaxLibDist = 4;
 constexpr uint32_t kCertUlps = 32;
 // float_certain's rare ranges (float inf / zero / subnormal results), out of

@@ -12,7 +12,7 @@ from conftest import ROOT
 PKG = os.path.join(ROOT, "path-tracing...but-on-the-lumi-cluster_amd")
 REQUIRED = ("-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize")
 RECIPES = [os.path.join(PKG, "csrc", "Makefile"), os.path.join(ROOT, "tests", "device_dropin", "Makefile"),
-           os.path.join(ROOT, "tools", "exhaustive_f64.sh")]
+           os.path.join(ROOT, "tests", "math_probe", "Makefile"), os.path.join(ROOT, "tools", "exhaustive_f64.sh")]
 
 
 def test_exact_build_recipes_carry_the_flags():
