@@ -78,10 +78,15 @@ def build_test_kernels(verbose=False):
 
 def build_tools(verbose=False):
     """tools/_bin/walk_sim: the CPU model of the block walk over the upload's own
-    packing (tests/test_block_bvh.py), and tests/frame_records/_bin/records_test,
-    the CPU test of the upload's per-frame records (tests/test_frame_records.py)."""
+    packing (tests/test_block_bvh.py), tests/frame_records/_bin/records_test,
+    the CPU test of the upload's per-frame records (tests/test_frame_records.py),
+    and tests/plane_set/_bin/plane_set_test, the CPU test of the outputs check and
+    the tile pack carving (tests/test_plane_set.py; like tests/math_probe it
+    belongs to the tests beside it and is built where they are)."""
     _run(["make", "walk_sim"], os.path.join(ROOT, "tools"), verbose)
     _run(["make"], os.path.join(ROOT, "tests", "frame_records"), verbose)
+    if os.path.exists(os.path.join(ROOT, "tests", "plane_set", "Makefile")):
+        _run(["make"], os.path.join(ROOT, "tests", "plane_set"), verbose)
 
 
 def prepare_assets():

@@ -1,15 +1,19 @@
 // Device functions on finished colours and luminance moments, each defined
 // once for the two units that use them: the render unit's folds
-// (pt_kernels.hip: k_accumulate, k_ad_fold, k_ad_resolve, ad_noisy) and the
-// image-space filters (image_ops.hip).  Only ref_math.h is needed: no ray, no
-// scene, no path state.
+// (pt_kernels.hip: k_accumulate, k_fold_features, k_ad_fold, k_resolve,
+// ad_noisy) and the image-space filters (image_ops.hip).  Only ref_math.h and
+// the plane set (host/planes.h) are needed: no ray, no scene, no path state.
 //
 //   finite3()                        every component finite
 //   aces(), srgb(), tonemap()        tonemap_pixel (path_tracer.hh:753-771)
 //   lum709()                         Rec. 709 luminance
 //   var_of_mean(), moments_of()      the luminance moments' closing arithmetic
+//   as_f4(), as_uc4()                ptg.h's pixel types as HIP's vector types
+//   close_radiance(), close_moments(), close_feature()
+//                                    a pixel's running sums closed into its planes
 #pragma once
 #include "ref_math.h"
+#include "host/planes.h"
 
 namespace ptg {
 namespace dm {
@@ -49,6 +53,40 @@ __device__ __forceinline__ float4 moments_of(float s1, float s2, uint32_t n)
     const float nf = (float)n;
     const float m1 = s1 / nf, m2 = s2 / nf;
     return make_float4(m1, m2, var_of_mean(m1, m2, nf), nf);
+}
+
+// ptg.h's pixel types (the plane set's) as the HIP vector types of the same layout
+__host__ __device__ __forceinline__ float4* as_f4(ptg_float4* p) { return reinterpret_cast<float4*>(p); }
+__host__ __device__ __forceinline__ uchar4* as_uc4(ptg_uchar4* p) { return reinterpret_cast<uchar4*>(p); }
+
+// The closing arithmetic: pixel p's running sums (Sums) into its planes
+// (Planes).  Its one home: the last chunk of the folds (k_accumulate,
+// k_fold_features: div = spp) and the deferred resolve (k_resolve: spp, the
+// samples taken, or the pixel's own count) all call these, so their bits are
+// the same by construction.  Every division is one correctly rounded float32
+// division of the sum by `div`: no reciprocal, no reordering.
+//
+// The radiance sum / div into out.accum and its tonemap into out.bgra, each
+// where the output is given.  `inside` false (a tile map's queue pixel outside
+// the image): zeros in both.
+PTG_D void close_radiance(float sx, float sy, float sz, float div, bool inside, const Planes& out, uint32_t p)
+{
+    const float ax = sx / div, ay = sy / div, az = sz / div;
+    if(out.accum) as_f4(out.accum)[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if(out.bgra) as_uc4(out.bgra)[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
+}
+// The luminance sums (s1, s2) of n finite samples into out.moments, which the
+// caller knows to be given; zeros outside the image and where n = 0.
+PTG_D void close_moments(float s1, float s2, uint32_t n, bool inside, const Planes& out, uint32_t p)
+{
+    as_f4(out.moments)[p] = inside && n > 0 ? moments_of(s1, s2, n) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// One feature plane's four sums / div into `plane` (out.albedo or
+// out.normal_depth, given).  Whether a pixel outside the image is written at
+// all is the caller's: the folds skip it, as k_features does.
+PTG_D void close_feature(float4 sum, float div, ptg_float4* plane, uint32_t p)
+{
+    as_f4(plane)[p] = make_float4(sum.x / div, sum.y / div, sum.z / div, sum.w / div);
 }
 
 } // namespace dm

@@ -22,17 +22,24 @@
 //   k_fold_features the same sums from the features round 0 of a fused render
 //                   stored per sample (ptg_render_with_features: k_wf_shade /
 //                   k_wf_sky with FEAT), folded beside k_accumulate
-//   k_ad_select<ALL>, k_ad_fold, k_ad_resolve
+//   k_ad_select<ALL>, k_ad_fold
 //                   adaptive sampling (ptg_render_adaptive): the stopping rule
-//                   compacted into a pixel list, the fold over that list, the
-//                   final division (its camera is k_wf_camera over AdaptivePass)
-//   k_accum_resolve progressive rendering (ptg_accum_*): the caller's running
-//                   sums divided and tonemapped without ending the accumulation
-//                   (its folds are k_accumulate and k_fold_features themselves)
+//                   compacted into a pixel list, the fold over that list (its
+//                   camera is k_wf_camera over AdaptivePass)
+//   k_resolve<PER_PIXEL>  the deferred resolve: running sums divided and
+//                   tonemapped outside a fold - ptg_render_adaptive's final
+//                   division by each pixel's own count, and ptg_accum_resolve,
+//                   which does not end the accumulation (the folds of both
+//                   are k_ad_fold / k_accumulate and k_fold_features)
+//
+// A frame's five planes and the three sums they are closed from travel as
+// Planes and Sums (host/planes.h); the closing arithmetic is
+// device/image_math.h's close_*.
 //
 // No fallback path exists: every entry point fails loudly (negative code +
 // ptg_last_error) when HIP or the device is unavailable.
 #include "runtime.h"
+#include "host/planes.h"
 #include "device/image_math.h"
 #include "device/path_tracer.h"
 #include "device/wavefront.h"
@@ -754,7 +761,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(DevScene sc, PixelMap pm, uint
 }
 
 // The fold's arithmetic, each operation one float32 rounding (k_accumulate,
-// k_ad_fold, k_ad_resolve, tp_blend and ad_noisy share it).
+// k_ad_fold, image_math.h's close_*, tp_blend and ad_noisy share it).
 //
 // A chunk's nj samples of queue pixel q (npix queue pixels) added, in sample
 // order, to the running radiance sum and, with MOMENTS, to the luminance
@@ -784,13 +791,14 @@ __device__ __forceinline__ void fold_samples(const float4* samples, uint32_t npi
 // MOMENTS (ptg_render_moments): in the same pass over the chunk, the first two
 // luminance moments of the finite samples too; the radiance sum is the same
 // operation for operation.  mom[p] = (s1, s2, n as bits, -) carries across
-// chunks as acc does; on the last chunk out_moments[p] = (m1, m2, variance of
-// the mean, n), normalised by n.  Without MOMENTS both pointers may be null.
+// chunks as acc does; on the last chunk out.moments[p] = (m1, m2, variance of
+// the mean, n), normalised by n, written unconditionally.  Without MOMENTS
+// neither mom nor out.moments is touched: both may be null.  A queue pixel
+// outside the image (tile maps) closes to zeros.
 template<bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj, const float4* __restrict__ samples,
                                                        float4* __restrict__ acc, float4* __restrict__ mom, int first,
-                                                       int last, float spp, float4* __restrict__ out_accum,
-                                                       uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments)
+                                                       int last, float spp, Planes out)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if(p >= pm.npix) return;
@@ -814,14 +822,10 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
         if constexpr(MOMENTS) mom[p] = make_float4(s1, s2, __uint_as_float(n), 0.f);
         return;
     }
-    ax = ax / spp;
-    ay = ay / spp;
-    az = az / spp;
     uint32_t x, y;
     const bool inside = pm.pixel(p, x, y);
-    if(out_accum) out_accum[p] = inside ? make_float4(ax, ay, az, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if(out_bgra) out_bgra[p] = inside ? tonemap(V3(ax, ay, az)) : make_uchar4(0, 0, 0, 0);
-    if constexpr(MOMENTS) out_moments[p] = inside && n > 0 ? moments_of(s1, s2, n) : make_float4(0.f, 0.f, 0.f, 0.f);
+    close_radiance(ax, ay, az, spp, inside, out, p);
+    if constexpr(MOMENTS) close_moments(s1, s2, n, inside, out, p);
 }
 
 // The feature fold of a fused render (ptg_render_with_features), beside
@@ -829,14 +833,14 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(PixelMap pm, uint32_t nj,
 // features (shade_path's FEAT stores, laid out like the samples) added in
 // sample order to eight running sums per pixel, which start from +0 and carry
 // across chunks in facc ([0, npix) albedo + coverage, [npix, 2 npix) normal +
-// depth); on the last chunk each sum / spp.  Per component that is k_features'
+// depth); on the last chunk each sum / spp into out.albedo and
+// out.normal_depth (both given).  Per component that is k_features'
 // arithmetic, acc = acc + v then acc / spp, so the bits are its bits.  Every
 // value is read once: non-temporal loads, as the radiance fold's.
 __global__ __launch_bounds__(kBlock) void k_fold_features(PixelMap pm, uint32_t nj, const float4* __restrict__ albedo,
                                                           const float4* __restrict__ normal_depth,
                                                           float4* __restrict__ facc, int first, int last, float spp,
-                                                          float4* __restrict__ out_albedo,
-                                                          float4* __restrict__ out_normal_depth)
+                                                          Planes out)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if(p >= pm.npix) return;
@@ -861,8 +865,8 @@ __global__ __launch_bounds__(kBlock) void k_fold_features(PixelMap pm, uint32_t 
     }
     uint32_t x, y;
     if(!pm.pixel(p, x, y)) return;   // as k_features: a pixel outside the image is not written
-    out_albedo[p] = make_float4(a.x / spp, a.y / spp, a.z / spp, a.w / spp);
-    out_normal_depth[p] = make_float4(n.x / spp, n.y / spp, n.z / spp, n.w / spp);
+    close_feature(a, spp, out.albedo, p);
+    close_feature(n, spp, out.normal_depth, p);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sample_list(DevScene sc, uint32_t n, const uint2* __restrict__ xy,
@@ -911,16 +915,13 @@ __global__ void k_scatter_tiles(PixelMap pm, const uchar4* __restrict__ tiles, u
 // slots.  Tile t = rank t % world's tile t / world; the pixel's slot is the
 // same in all five planes of that rank's pack.  Pure copies: 16-byte loads
 // (4 for the bytes), non-temporal since every slot is read once.  The host
-// checked that pack_tiles covers every rank's tiles, so slot < slots.
-struct AssembleOut {
-    float4 *accum, *moments, *albedo, *normal_depth;   // each may be null
-    uint32_t* bgra;                                    // a uchar4 pixel as one word
-};
-
+// checked that pack_tiles covers every rank's tiles, so slot < slots.  The
+// rank's pack is carved by pack_planes, as the render that wrote it carved it
+// (the packs are only read); a uchar4 pixel moves as one word.
 __global__ __launch_bounds__(kBlock) void k_assemble_tile_packs(uint32_t img_w, uint32_t npix, uint32_t tw, uint32_t th,
                                                                 uint32_t tiles_x, uint32_t world, uint32_t slots,
                                                                 size_t pack_bytes, const uint8_t* __restrict__ packs,
-                                                                AssembleOut out)
+                                                                Planes out)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if(p >= npix) return;
@@ -929,14 +930,13 @@ __global__ __launch_bounds__(kBlock) void k_assemble_tile_packs(uint32_t img_w, 
     const uint32_t t = ty * tiles_x + tx;
     const uint32_t rank = t % world, k = t / world;
     const uint32_t slot = k * (tw * th) + (y - ty * th) * tw + (x - tx * tw);
-    const uint8_t* pack = packs + size_t(rank) * pack_bytes;
-    const float4* planes = reinterpret_cast<const float4*>(pack);
-    if(out.accum) out.accum[p] = nt_load(planes + slot);
-    if(out.moments) out.moments[p] = nt_load(planes + size_t(slots) + slot);
-    if(out.albedo) out.albedo[p] = nt_load(planes + 2 * size_t(slots) + slot);
-    if(out.normal_depth) out.normal_depth[p] = nt_load(planes + 3 * size_t(slots) + slot);
+    const Planes in = pack_planes(const_cast<uint8_t*>(packs) + size_t(rank) * pack_bytes, slots);
+    if(out.accum) as_f4(out.accum)[p] = nt_load(as_f4(in.accum) + slot);
+    if(out.moments) as_f4(out.moments)[p] = nt_load(as_f4(in.moments) + slot);
+    if(out.albedo) as_f4(out.albedo)[p] = nt_load(as_f4(in.albedo) + slot);
+    if(out.normal_depth) as_f4(out.normal_depth)[p] = nt_load(as_f4(in.normal_depth) + slot);
     if(out.bgra)
-        out.bgra[p] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(pack + 64 * size_t(slots)) + slot);
+        reinterpret_cast<uint32_t*>(out.bgra)[p] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(in.bgra) + slot);
 }
 
 // ---- first-hit feature buffers (the a-trous denoiser over them: image_ops.hip) ----
@@ -1152,71 +1152,40 @@ __global__ __launch_bounds__(kBlock) void k_ad_fold(AdaptivePass ad, uint32_t nj
     mom[pix] = make_float4(s1, s2, __uint_as_float(n), 0.f);
 }
 
-// Resolve, one work-item per rectangle pixel: the radiance sum over the
-// pixel's own sample count, its tonemap, the moments as k_accumulate<true>
-// ends, and the count.  Each output may be null.
-__global__ __launch_bounds__(kBlock) void k_ad_resolve(uint32_t npix, const float4* __restrict__ acc,
-                                                       const float4* __restrict__ mom, float4* __restrict__ out_accum,
-                                                       uchar4* __restrict__ out_bgra, float4* __restrict__ out_moments,
-                                                       uint32_t* __restrict__ out_samples)
+// The deferred resolve, one work-item per rectangle pixel: running sums `s`
+// (only read) closed into the planes of `out` as the folds' last chunk closes
+// them (image_math.h's close_*), outside any fold.  Each output may be null,
+// and the plane behind a null output is not loaded: s.mom and s.feat may then
+// be null too.
+// PER_PIXEL = false (ptg_accum_resolve): every sum / div, the caller's spp or
+// the samples the state holds.
+// PER_PIXEL = true (ptg_render_adaptive): the divisor is the pixel's own
+// sample count, acc.w as bits (k_ad_fold), which also goes to out_samples
+// where given; `div` is not read.
+template<bool PER_PIXEL>
+__global__ __launch_bounds__(kBlock) void k_resolve(uint32_t npix, Sums s, float div, Planes out,
+                                                    uint32_t* __restrict__ out_samples)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if(p >= npix) return;
-    const float4 a = acc[p];
-    const uint32_t ns = __float_as_uint(a.w);
-    const float nsf = (float)ns;
-    const float ax = a.x / nsf, ay = a.y / nsf, az = a.z / nsf;
-    if(out_accum) out_accum[p] = make_float4(ax, ay, az, 0.f);
-    if(out_bgra) out_bgra[p] = tonemap(V3(ax, ay, az));
-    if(out_moments)
+    if(PER_PIXEL || out.accum || out.bgra)
     {
-        const float4 mo = mom[p];
-        const uint32_t n = __float_as_uint(mo.z);
-        out_moments[p] = n > 0 ? moments_of(mo.x, mo.y, n) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 a = as_f4(s.acc)[p];
+        if constexpr(PER_PIXEL)
+        {
+            const uint32_t ns = __float_as_uint(a.w);
+            div = (float)ns;
+            if(out_samples) out_samples[p] = ns;
+        }
+        close_radiance(a.x, a.y, a.z, div, true, out, p);
     }
-    if(out_samples) out_samples[p] = ns;
-}
-
-// ptg_accum_resolve, one work-item per rectangle pixel: the caller's planes
-// (ptg.h's state layout: acc, then mom and the two planes of feat where the
-// state has them) closed as the folds' last chunk closes the context's sums -
-// each sum / div in one rounding (k_accumulate's and k_fold_features' last
-// branch, div = spp there), tonemap of the radiance written, moments_of the
-// luminance sums.  The planes are only read.  Each output may be null; a
-// null output's plane is not loaded (mom and feat may then be null too).
-__global__ __launch_bounds__(kBlock) void k_accum_resolve(uint32_t npix, const float4* __restrict__ acc,
-                                                          const float4* __restrict__ mom,
-                                                          const float4* __restrict__ feat, float div,
-                                                          float4* __restrict__ out_accum, uchar4* __restrict__ out_bgra,
-                                                          float4* __restrict__ out_moments,
-                                                          float4* __restrict__ out_albedo,
-                                                          float4* __restrict__ out_normal_depth)
-{
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if(p >= npix) return;
-    if(out_accum || out_bgra)
+    if(out.moments)
     {
-        const float4 a = acc[p];
-        const float ax = a.x / div, ay = a.y / div, az = a.z / div;
-        if(out_accum) out_accum[p] = make_float4(ax, ay, az, 0.f);
-        if(out_bgra) out_bgra[p] = tonemap(V3(ax, ay, az));
+        const float4 mo = as_f4(s.mom)[p];
+        close_moments(mo.x, mo.y, __float_as_uint(mo.z), true, out, p);
     }
-    if(out_moments)
-    {
-        const float4 mo = mom[p];
-        const uint32_t n = __float_as_uint(mo.z);
-        out_moments[p] = n > 0 ? moments_of(mo.x, mo.y, n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if(out_albedo)
-    {
-        const float4 a = feat[p];
-        out_albedo[p] = make_float4(a.x / div, a.y / div, a.z / div, a.w / div);
-    }
-    if(out_normal_depth)
-    {
-        const float4 n = feat[npix + p];
-        out_normal_depth[p] = make_float4(n.x / div, n.y / div, n.z / div, n.w / div);
-    }
+    if(out.albedo) close_feature(as_f4(s.feat)[p], div, out.albedo, p);
+    if(out.normal_depth) close_feature(as_f4(s.feat)[npix + p], div, out.normal_depth, p);
 }
 
 // ---------------------------------------------------------- render driver --
@@ -1295,16 +1264,6 @@ int launch(ptg_context* ctx, int kind, hipStream_t st, dim3 grid, uint32_t lds, 
     return timed_end(ctx, st);
 }
 
-// The running sums of a progressive render (ptg_accum_*), which belong to the
-// caller: the planes of ptg.h's state layout, laid out and summed as the
-// context's own acc, mom and feat_acc are.  mom and feat are null where the
-// state has no such plane.
-struct FoldPlanes {
-    float4* acc = nullptr;    // the radiance sums
-    float4* mom = nullptr;    // (s1, s2, n as bits, 0)
-    float4* feat = nullptr;   // two planes: albedo + coverage, normal + depth
-};
-
 // A render call's fixed parts, shared by the steps render_map and
 // render_adaptive are made of.
 struct RenderJob {
@@ -1312,8 +1271,20 @@ struct RenderJob {
     const ptg_render_config* cfg;
     PixelMap pm;                           // in a pass of render_adaptive only npix counts: the list's length
     uint32_t j0, j1;                       // the sample range
-    float4* out_accum;
-    uchar4* out_bgra;
+    // what the range's last fold closes (render_adaptive: its resolve); with
+    // albedo and normal_depth (both or neither, wavefront only) the render is
+    // a fused one: round 0 stores the first-hit features per sample and
+    // fold_chunk folds them too
+    Planes out;
+    // the running sums the folds carry, and only those: mom where the fold
+    // keeps the luminance moments, feat in a fused render.  The context's own
+    // (acc, mom, feat_acc: render_map sets them once they are grown), or with
+    // `carried` the caller's (ptg_accum_add): then no chunk is the first or the
+    // last and nothing is closed
+    Sums sums;
+    bool carried = false;
+    bool moments() const { return out.moments != nullptr || sums.mom != nullptr; }
+    bool fused() const { return out.albedo != nullptr || sums.feat != nullptr; }
     const AdaptivePass* ad = nullptr;      // render_adaptive: the pass whose list the chunks are traced and folded over
     uint32_t pipelines = 1;                // chunk pipelines (slots) in use
     uint32_t chunk = 0;                    // samples per chunk
@@ -1324,16 +1295,6 @@ struct RenderJob {
     size_t spill_region = 0;               // walk stack spill entries per (slot, walk kind)
     unsigned long long* cnt = nullptr;     // counting renders: the device counters
     uint32_t prev_slot = 0xFFFFFFFFu;      // the slot of the last fold
-    float4* out_moments = nullptr;         // ptg_render_moments: the fold also keeps the luminance moments
-    // ptg_render_with_features on the wavefront pipeline (both or neither): round 0
-    // stores the first-hit features per sample, fold_chunk folds them too
-    float4 *out_albedo = nullptr, *out_normal_depth = nullptr;
-    // ptg_accum_add: fold into these planes, the caller's, and do not resolve
-    // (fold_chunk); with keep.mom the fold keeps the moments, with keep.feat
-    // the render is a fused one
-    FoldPlanes keep;
-    bool moments() const { return out_moments != nullptr || keep.mom != nullptr; }
-    bool fused() const { return out_albedo != nullptr || keep.feat != nullptr; }
     // slot k's per-sample feature arrays, each pm.npix * chunk entries
     FeatOut<true> feat_of(uint32_t k) const
     {
@@ -1626,8 +1587,9 @@ int trace_chunk_wavefront(RenderJob& job, const Piece& pc, const Piece* next = n
 // A slot's next chunk then reuses its samples buffer after its fold in
 // stream order, with no event at all.  A render that keeps the samples'
 // moments (ptg_render_moments) folds with k_accumulate<true>, in the same
-// place and order; k_accumulate<false> touches neither ctx->mom nor the
-// null out_moments.  A fused render (ptg_render_with_features) folds the
+// place and order; k_accumulate<false> touches neither the moment sums nor
+// out.moments (both null then).  The sums are job.sums, whoever owns them.
+// A fused render (ptg_render_with_features) folds the
 // chunk's features with k_fold_features right behind it, ahead of the event:
 // the feature sums follow the same chain.  A pass of render_adaptive folds
 // with k_ad_fold over its list; job.prev_slot runs through the whole render,
@@ -1636,29 +1598,25 @@ int fold_chunk(RenderJob& job, const Piece& pc)
 {
     ptg_context* ctx = job.ctx;
     ptg_context::Slot& sl = ctx->slot[pc.slot];
-    // ptg_accum_add (job.keep): the sums are the caller's planes and no chunk
+    // ptg_accum_add (job.carried): the sums are the caller's planes and no chunk
     // is the first or the last - the fold reads them, adds and writes them back
     // (a zeroed plane starts from +0 as `first` does), and divides nothing
-    const bool kept = job.keep.acc != nullptr;
-    const int first = !kept && pc.j == job.j0, last = !kept && pc.j + pc.n >= job.j1;
-    float4* const acc = kept ? job.keep.acc : ctx->acc.as<float4>();
-    float4* const mom = kept ? job.keep.mom : ctx->mom.as<float4>();
-    float4* const facc = kept ? job.keep.feat : ctx->feat_acc.as<float4>();
+    const int first = !job.carried && pc.j == job.j0, last = !job.carried && pc.j + pc.n >= job.j1;
+    float4 *const acc = as_f4(job.sums.acc), *const mom = as_f4(job.sums.mom);
     const hipStream_t as = ctx->main_of(pc.slot);
     if(job.pipelines > 1 && job.prev_slot != 0xFFFFFFFFu && job.prev_slot != pc.slot)
         PTG_HIP(hipStreamWaitEvent(as, ctx->slot[job.prev_slot].ev_acc, 0));
     const auto fold = job.moments() ? k_accumulate<true> : k_accumulate<false>;
     const dim3 grid(grid_for(job.pm.npix));
-    if(int r = job.ad ? launch(ctx, K_ACCUM, as, grid, 0, k_ad_fold, k_ad_fold, *job.ad, pc.n, sl.samples.as<float4>(),
-                               ctx->acc.as<float4>(), ctx->mom.as<float4>())
+    if(int r = job.ad ? launch(ctx, K_ACCUM, as, grid, 0, k_ad_fold, k_ad_fold, *job.ad, pc.n, sl.samples.as<float4>(), acc, mom)
                       : launch(ctx, K_ACCUM, as, grid, 0, fold, fold, job.pm, pc.n, sl.samples.as<float4>(), acc, mom, first,
-                               last, (float)job.cfg->samples_per_pixel, job.out_accum, job.out_bgra, job.out_moments))
+                               last, (float)job.cfg->samples_per_pixel, job.out))
         return r;
     if(job.fused())
     {   // the features of the chunk, directly behind its samples: same stream, same order, same event
         const FeatOut<true> f = job.feat_of(pc.slot);
         if(int r = launch(ctx, K_ACCUM, as, grid, 0, k_fold_features, k_fold_features, job.pm, pc.n, f.albedo, f.normal_depth,
-                          facc, first, last, (float)job.cfg->samples_per_pixel, job.out_albedo, job.out_normal_depth))
+                          as_f4(job.sums.feat), first, last, (float)job.cfg->samples_per_pixel, job.out))
             return r;
     }
     if(job.pipelines > 1) PTG_HIP(hipEventRecord(sl.ev_acc, as));
@@ -1758,18 +1716,18 @@ int join_folds(const RenderJob& job)
     return PTG_OK;
 }
 
-// Render the pixels of `pm` for samples [j0, j1): per chunk of samples, the
-// path kernels write one float4 per (pixel, sample); k_accumulate folds the
-// chunk into the running per-pixel sum in sample order.
-// With out_albedo / out_normal_depth (wavefront only: ptg_render_with_features)
+// Render the pixels of `pm` for samples [j0, j1) into the planes of `out`: per
+// chunk of samples, the path kernels write one float4 per (pixel, sample);
+// k_accumulate folds the chunk into the running per-pixel sum in sample order,
+// with out.moments the luminance moments too.
+// With out.albedo and out.normal_depth (both; wavefront only: render_planes)
 // round 0 also stores every sample's first-hit features and k_fold_features
 // folds them.
-// With `keep` (ptg_accum_add; no outputs beside it) the chunks fold into the
-// caller's planes, moments and features as the planes say, and nothing is
-// resolved: the context's own sums are not touched.
-int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1,
-               ptg_float4* out_accum, ptg_uchar4* out_bgra, ptg_float4* out_moments = nullptr,
-               ptg_float4* out_albedo = nullptr, ptg_float4* out_normal_depth = nullptr, const FoldPlanes* keep = nullptr)
+// With `carried` (ptg_accum_add; `out` empty) the chunks fold into the
+// caller's sums, moments and features as the sums say, and nothing is
+// closed: the context's own sums are not touched.
+int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint32_t j0, uint32_t j1, const Planes& out,
+               const Sums* carried = nullptr)
 {
     if(pm.npix == 0) return PTG_OK;
     if(j1 <= j0) return fail(PTG_E_INVALID, "empty sample range");
@@ -1777,26 +1735,29 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
     if(!wf && ctx->stack_bound >= PrivStack::kCap)
         return fail(PTG_E_RANGE, "the megakernel's walk stack holds " + std::to_string(PrivStack::kCap) +
                                      " entries, this frame's BVHs need " + std::to_string(ctx->stack_bound));
-    RenderJob job{ctx, cfg, pm, j0, j1, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra)};
-    if(out_albedo && out_normal_depth)
+    RenderJob job{ctx, cfg, pm, j0, j1, out};
+    if(carried)
     {
-        if(!wf) return fail(PTG_E_INVALID, "render_map: fused features run on the wavefront pipeline");
-        job.out_albedo = reinterpret_cast<float4*>(out_albedo);
-        job.out_normal_depth = reinterpret_cast<float4*>(out_normal_depth);
+        job.sums = *carried;
+        job.carried = true;
     }
-    if(keep)
-    {
-        if(keep->feat && !wf) return fail(PTG_E_INVALID, "render_map: fused features run on the wavefront pipeline");
-        job.keep = *keep;
-    }
+    if(job.fused() && !wf) return fail(PTG_E_INVALID, "render_map: fused features run on the wavefront pipeline");
     if(int r = begin_render(job, wf)) return r;
     if(int r = size_chunks(job, wf)) return r;
-    if(!keep) PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
-    if(job.fused() && !keep) PTG_HIP(ctx->grow(ctx->feat_acc, 2 * size_t(pm.npix) * sizeof(float4)));
-    if(out_moments)
-    {
-        job.out_moments = reinterpret_cast<float4*>(out_moments);
-        PTG_HIP(ctx->grow(ctx->mom, size_t(pm.npix) * sizeof(float4)));
+    if(!carried)
+    {   // the context's own sums, grown to the map
+        PTG_HIP(ctx->grow(ctx->acc, size_t(pm.npix) * sizeof(float4)));
+        job.sums.acc = ctx->acc.as<ptg_float4>();
+        if(job.fused())
+        {
+            PTG_HIP(ctx->grow(ctx->feat_acc, 2 * size_t(pm.npix) * sizeof(float4)));
+            job.sums.feat = ctx->feat_acc.as<ptg_float4>();
+        }
+        if(out.moments)
+        {
+            PTG_HIP(ctx->grow(ctx->mom, size_t(pm.npix) * sizeof(float4)));
+            job.sums.mom = ctx->mom.as<ptg_float4>();
+        }
     }
     if(int r = start_slots(job)) return r;
     const std::vector<Piece> plan = plan_chunks(job);
@@ -1817,23 +1778,24 @@ int render_map(ptg_context* ctx, const ptg_render_config* cfg, PixelMap pm, uint
 // ctx->ad_list (job.ad; size_chunks / plan_chunks with npix = the list's
 // length); after a pass from min_passes on, k_ad_select rebuilds the list from
 // the running sums and the host reads its length - the render's only wait.
-// The running sums are ctx->acc and ctx->mom, indexed by rectangle pixel.
+// The running sums (job.sums) are ctx->acc and ctx->mom, indexed by rectangle
+// pixel; k_resolve<true> closes them into `out` and out_samples.
 int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelMap& rect, const ptg_adaptive_params& P,
-                    float4* out_accum, uchar4* out_bgra, float4* out_moments, uint32_t* out_samples)
+                    const Planes& out, uint32_t* out_samples)
 {
     ctx->ad_passes_run = 0;
     for(uint64_t& a: ctx->ad_active) a = 0;
     const uint32_t npix = rect.npix;
     if(npix == 0) return PTG_OK;
-    RenderJob job{ctx, cfg, rect, 0, cfg->samples_per_pixel / P.passes, nullptr, nullptr};
+    RenderJob job{ctx, cfg, rect, 0, cfg->samples_per_pixel / P.passes, out};
     PTG_HIP(ctx->grow(ctx->acc, size_t(npix) * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->mom, size_t(npix) * sizeof(float4)));
     PTG_HIP(ctx->grow(ctx->ad_list, size_t(npix) * sizeof(uint32_t)));
     PTG_HIP(ctx->grow(ctx->ad_count, 256));
     uint32_t* list = ctx->ad_list.as<uint32_t>();
     uint32_t* count = ctx->ad_count.as<uint32_t>();
-    float4* acc = ctx->acc.as<float4>();
-    float4* mom = ctx->mom.as<float4>();
+    job.sums = Sums{ctx->acc.as<ptg_float4>(), ctx->mom.as<ptg_float4>()};
+    float4 *const acc = as_f4(job.sums.acc), *const mom = as_f4(job.sums.mom);
     if(int r = begin_render(job, true)) return r;
     // the sums start from +0; before min_passes every pixel is active.  The
     // other slots start behind the zeroed sums and the first list.
@@ -1868,8 +1830,7 @@ int render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, const PixelM
         if(len > npix) return fail(PTG_E_RANGE, "ptg_render_adaptive: the active list is longer than the rectangle");
     }
     if(int r = join_folds(job)) return r;
-    if(int r = launch_plain(ctx, grid_for(npix), k_ad_resolve, npix, acc, mom, out_accum, out_bgra, out_moments, out_samples))
-        return r;
+    if(int r = launch_plain(ctx, grid_for(npix), k_resolve<true>, npix, job.sums, 0.0f, out, out_samples)) return r;
     return end_render(ctx);
 }
 
@@ -2017,7 +1978,7 @@ int ptg_render(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint
     if(int r = check_cfg(ctx, cfg, sample_end)) return r;
     PixelMap pm;
     if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
-    return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra);
+    return render_map(ctx, cfg, pm, sample_begin, sample_end, Planes{out_accum, out_bgra});
 }
 
 int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -2029,7 +1990,7 @@ int ptg_render_moments(ptg_context* ctx, const ptg_render_config* cfg, uint32_t 
     if(!out_moments) return fail(PTG_E_INVALID, "ptg_render_moments: null out_moments");
     PixelMap pm;
     if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
-    return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments);
+    return render_map(ctx, cfg, pm, sample_begin, sample_end, Planes{out_accum, out_bgra, out_moments});
 }
 
 void ptg_adaptive_params_default(ptg_adaptive_params* p)
@@ -2064,8 +2025,7 @@ int ptg_render_adaptive(ptg_context* ctx, const ptg_render_config* cfg, uint32_t
         return fail(PTG_E_INVALID, "ptg_render_adaptive: runs on the wavefront pipeline only (ptg_set_pipeline(ctx, 0))");
     PixelMap pm;
     if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
-    return render_adaptive(ctx, cfg, pm, P, reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra),
-                           reinterpret_cast<float4*>(out_moments), out_samples);
+    return render_adaptive(ctx, cfg, pm, P, Planes{out_accum, out_bgra, out_moments}, out_samples);
 }
 
 int ptg_last_adaptive_stats(ptg_context* ctx, uint32_t* passes_run, uint64_t active[16])
@@ -2099,7 +2059,7 @@ int ptg_render_tiles(ptg_context* ctx, const ptg_render_config* cfg, uint32_t ti
     if(int r = check_cfg(ctx, cfg, cfg ? cfg->samples_per_pixel : 0)) return r;
     PixelMap pm;
     if(int r = tile_map(cfg, tile_w, tile_h, first_tile, tile_stride, tile_count, pm)) return r;
-    return render_map(ctx, cfg, pm, 0, cfg->samples_per_pixel, out_accum, out_bgra);
+    return render_map(ctx, cfg, pm, 0, cfg->samples_per_pixel, Planes{out_accum, out_bgra});
 }
 
 int ptg_scatter_tiles(ptg_context* ctx, const ptg_render_config* cfg, uint32_t tile_w, uint32_t tile_h,
@@ -2352,6 +2312,21 @@ static int features_map(ptg_context* ctx, const ptg_render_config* cfg, const Pi
                         reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth));
 }
 
+// All five planes of `out` (the feature planes given) over the pixels of `pm`:
+// one fused render on the wavefront pipeline; the megakernel keeps no path
+// state between kernels, so there the render without the feature planes, then
+// the feature pass - the same bits.
+static int render_planes(ptg_context* ctx, const ptg_render_config* cfg, const PixelMap& pm, uint32_t j0, uint32_t j1,
+                         const Planes& out)
+{
+    if(ctx->pipeline == 0) return render_map(ctx, cfg, pm, j0, j1, out);
+    if(int r = render_map(ctx, cfg, pm, j0, j1, Planes{out.accum, out.bgra, out.moments})) return r;
+    return features_map(ctx, cfg, pm, j0, j1, out.albedo, out.normal_depth);
+}
+
+// check_planes' verdict (host/planes.h) as an entry's return: the message set where it refuses
+static int refused(const PlanesVerdict& v) { return v.code == PTG_OK ? PTG_OK : fail(v.code, v.message); }
+
 int ptg_render_features(ptg_context* ctx, const ptg_render_config* cfg, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                         uint32_t sample_begin, uint32_t sample_end, ptg_float4* out_albedo, ptg_float4* out_normal_depth)
 {
@@ -2372,37 +2347,20 @@ int ptg_render_with_features(ptg_context* ctx, const ptg_render_config* cfg, uin
     if(int r = bind(ctx)) return r;
     if(int r = check_cfg(ctx, cfg, sample_end)) return r;
     if(!out_albedo || !out_normal_depth) return fail(PTG_E_INVALID, "ptg_render_with_features: null feature output");
-    const void* outs[5] = {out_accum, out_bgra, out_moments, out_albedo, out_normal_depth};
-    for(int a = 0; a < 5; ++a)
-        for(int b = a + 1; b < 5; ++b)
-            if(outs[a] && outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_render_with_features: two outputs are the same buffer");
+    const Planes out{out_accum, out_bgra, out_moments, out_albedo, out_normal_depth};
+    if(int r = refused(check_planes("ptg_render_with_features", out, 0, nullptr, false, false))) return r;
     PixelMap pm;
     if(int r = rect_map(cfg, x0, y0, w, h, pm)) return r;
     if(pm.npix == 0) return PTG_OK;
     if(sample_end <= sample_begin) return fail(PTG_E_INVALID, "empty sample range");
-    if(ctx->pipeline != 0)
-    {   // the megakernel keeps no path state between kernels: the two passes, one after the other
-        if(int r = render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments)) return r;
-        return ptg_render_features(ctx, cfg, x0, y0, w, h, sample_begin, sample_end, out_albedo, out_normal_depth);
-    }
-    return render_map(ctx, cfg, pm, sample_begin, sample_end, out_accum, out_bgra, out_moments, out_albedo, out_normal_depth);
+    return render_planes(ctx, cfg, pm, sample_begin, sample_end, out);
 }
 
-// ---- tile packs: a tile shard's five planes in one buffer (ptg.h) ----
-
-// The slots of a pack, 0 when a dimension is 0 or they do not stay below 2^31.
-static uint64_t tile_pack_slots(uint32_t tw, uint32_t th, uint32_t pack_tiles)
-{
-    const uint64_t per = uint64_t(tw) * th;
-    if(per == 0 || pack_tiles == 0 || per >= (1ull << 31)) return 0;
-    const uint64_t slots = per * pack_tiles;   // below 2^63
-    return slots < (1ull << 31) ? slots : 0;
-}
+// ---- tile packs: a tile shard's five planes in one buffer (ptg.h; carved by host/planes.h) ----
 
 size_t ptg_tile_pack_bytes(uint32_t tile_w, uint32_t tile_h, uint32_t pack_tiles)
 {
-    const uint64_t slots = tile_pack_slots(tile_w, tile_h, pack_tiles);
-    return size_t((slots * (4 * sizeof(float4) + sizeof(uchar4)) + 255u) & ~uint64_t(255));
+    return tile_pack_bytes(tile_pack_slots(tile_w, tile_h, pack_tiles));
 }
 
 int ptg_render_tiles_packed(ptg_context* ctx, const ptg_render_config* cfg, uint32_t tile_w, uint32_t tile_h,
@@ -2422,18 +2380,9 @@ int ptg_render_tiles_packed(ptg_context* ctx, const ptg_render_config* cfg, uint
     if(slots == 0) return fail(PTG_E_RANGE, "ptg_render_tiles_packed: too many pack slots");
     // everything the render does not write - pixels outside the image in the
     // feature planes, the tiles behind tile_count, the padding - is 0
-    PTG_HIP(hipMemsetAsync(pack, 0, ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles), ctx->stream));
+    PTG_HIP(hipMemsetAsync(pack, 0, tile_pack_bytes(slots), ctx->stream));
     if(pm.npix == 0) return PTG_OK;
-    ptg_float4* planes = static_cast<ptg_float4*>(pack);
-    ptg_float4 *accum = planes, *moments = planes + slots, *albedo = planes + 2 * slots, *normal_depth = planes + 3 * slots;
-    ptg_uchar4* bgra = reinterpret_cast<ptg_uchar4*>(planes + 4 * slots);
-    const uint32_t spp = cfg->samples_per_pixel;
-    if(ctx->pipeline != 0)
-    {   // as ptg_render_with_features: the two passes, one after the other
-        if(int r = render_map(ctx, cfg, pm, 0, spp, accum, bgra, moments)) return r;
-        return features_map(ctx, cfg, pm, 0, spp, albedo, normal_depth);
-    }
-    return render_map(ctx, cfg, pm, 0, spp, accum, bgra, moments, albedo, normal_depth);
+    return render_planes(ctx, cfg, pm, 0, cfg->samples_per_pixel, pack_planes(pack, slots));
 }
 
 int ptg_assemble_tile_packs(ptg_context* ctx, const ptg_render_config* cfg, uint32_t tile_w, uint32_t tile_h, uint32_t world,
@@ -2455,27 +2404,10 @@ int ptg_assemble_tile_packs(ptg_context* ctx, const ptg_render_config* cfg, uint
                                      std::to_string(need));
     const uint64_t slots = tile_pack_slots(tile_w, tile_h, pack_tiles);
     if(slots == 0) return fail(PTG_E_RANGE, "ptg_assemble_tile_packs: too many pack slots");
-    const size_t pack_bytes = ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles);
-    const char* outs[5] = {reinterpret_cast<const char*>(out_accum), reinterpret_cast<const char*>(out_bgra),
-                           reinterpret_cast<const char*>(out_moments), reinterpret_cast<const char*>(out_albedo),
-                           reinterpret_cast<const char*>(out_normal_depth)};
-    const char* const lo = static_cast<const char*>(packs);
-    const char* const hi = lo + size_t(world) * pack_bytes;
-    bool any = false;
-    for(int a = 0; a < 5; ++a)
-    {
-        if(!outs[a]) continue;
-        any = true;
-        const size_t elem = a == 1 ? sizeof(uchar4) : sizeof(float4);
-        if(reinterpret_cast<uintptr_t>(outs[a]) % elem) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: a misaligned output");
-        for(int b = a + 1; b < 5; ++b)
-            if(outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: two outputs are the same buffer");
-        if(outs[a] < hi && outs[a] + npix * elem > lo) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: an output overlaps the packs");
-    }
-    if(!any) return fail(PTG_E_INVALID, "ptg_assemble_tile_packs: no output given");
-    const AssembleOut out{reinterpret_cast<float4*>(out_accum), reinterpret_cast<float4*>(out_moments),
-                          reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal_depth),
-                          reinterpret_cast<uint32_t*>(out_bgra)};
+    const size_t pack_bytes = tile_pack_bytes(slots);
+    const Planes out{out_accum, out_bgra, out_moments, out_albedo, out_normal_depth};
+    const ForbiddenRange gathered{packs, size_t(world) * pack_bytes, "overlaps the packs"};
+    if(int r = refused(check_planes("ptg_assemble_tile_packs", out, npix, &gathered, true, true))) return r;
     return launch_plain(ctx, grid_for(npix), k_assemble_tile_packs, cfg->width, uint32_t(npix), tile_w, tile_h, tiles_x, world,
                         uint32_t(slots), pack_bytes, static_cast<const uint8_t*>(packs), out);
 }
@@ -2505,12 +2437,12 @@ static int check_accum(const char* who, const ptg_accum* acc, const void* state)
     return PTG_OK;
 }
 
-// The planes of a state with the header's rectangle and flags.
-static FoldPlanes accum_planes(const ptg_accum& acc, void* state)
+// The sums of a state with the header's rectangle and flags.
+static Sums accum_sums(const ptg_accum& acc, void* state)
 {
     const size_t npix = size_t(acc.w) * acc.h;
-    FoldPlanes pl;
-    float4* next = static_cast<float4*>(state);
+    Sums pl;
+    ptg_float4* next = static_cast<ptg_float4*>(state);
     pl.acc = next;
     next += npix;
     if(acc.flags & PTG_ACCUM_MOMENTS)
@@ -2549,9 +2481,8 @@ int ptg_accum_add(ptg_context* ctx, ptg_accum* acc, void* state, uint32_t sample
     if(int r = rect_map(&cfg, acc->x0, acc->y0, acc->w, acc->h, pm)) return r;
     if((acc->flags & PTG_ACCUM_FEATURES) && ctx->pipeline != 0)
         return fail(PTG_E_INVALID, "ptg_accum_add: PTG_ACCUM_FEATURES runs on the wavefront pipeline only (ptg_set_pipeline(ctx, 0))");
-    const FoldPlanes planes = accum_planes(*acc, state);
-    if(int r = render_map(ctx, &cfg, pm, acc->sample_next, sample_end, nullptr, nullptr, nullptr, nullptr, nullptr, &planes))
-        return r;
+    const Sums sums = accum_sums(*acc, state);
+    if(int r = render_map(ctx, &cfg, pm, acc->sample_next, sample_end, Planes{}, &sums)) return r;
     acc->sample_next = sample_end;
     return PTG_OK;
 }
@@ -2569,29 +2500,13 @@ int ptg_accum_resolve(ptg_context* ctx, const ptg_accum* acc, const void* state,
         return fail(PTG_E_INVALID, "ptg_accum_resolve: a feature output of a state without PTG_ACCUM_FEATURES");
     const size_t npix = size_t(acc->w) * acc->h;
     if(npix >= (1ull << 31)) return fail(PTG_E_RANGE, "image too large");
-    const char* outs[5] = {reinterpret_cast<const char*>(out_accum), reinterpret_cast<const char*>(out_bgra),
-                           reinterpret_cast<const char*>(out_moments), reinterpret_cast<const char*>(out_albedo),
-                           reinterpret_cast<const char*>(out_normal_depth)};
-    const char* const lo = static_cast<const char*>(state);
-    const char* const hi = lo + ptg_accum_state_bytes(acc->w, acc->h, acc->flags);
-    bool any = false;
-    for(int a = 0; a < 5; ++a)
-    {
-        if(!outs[a]) continue;
-        any = true;
-        for(int b = a + 1; b < 5; ++b)
-            if(outs[a] == outs[b]) return fail(PTG_E_INVALID, "ptg_accum_resolve: two outputs are the same buffer");
-        const size_t bytes = npix * (a == 1 ? sizeof(uchar4) : sizeof(float4));
-        if(outs[a] < hi && outs[a] + bytes > lo) return fail(PTG_E_INVALID, "ptg_accum_resolve: an output lies inside the state");
-    }
-    if(!any) return fail(PTG_E_INVALID, "ptg_accum_resolve: no output given");
+    const Planes out{out_accum, out_bgra, out_moments, out_albedo, out_normal_depth};
+    const ForbiddenRange planes{state, ptg_accum_state_bytes(acc->w, acc->h, acc->flags), "lies inside the state"};
+    if(int r = refused(check_planes("ptg_accum_resolve", out, npix, &planes, true, false))) return r;
     if(npix == 0) return PTG_OK;
-    const FoldPlanes pl = accum_planes(*acc, const_cast<void*>(state));
     const float div = by_samples ? (float)(acc->sample_next - acc->sample_begin) : (float)acc->cfg.samples_per_pixel;
-    return launch_plain(ctx, grid_for(npix), k_accum_resolve, uint32_t(npix), pl.acc, pl.mom, pl.feat, div,
-                        reinterpret_cast<float4*>(out_accum), reinterpret_cast<uchar4*>(out_bgra),
-                        reinterpret_cast<float4*>(out_moments), reinterpret_cast<float4*>(out_albedo),
-                        reinterpret_cast<float4*>(out_normal_depth));
+    return launch_plain(ctx, grid_for(npix), k_resolve<false>, uint32_t(npix), accum_sums(*acc, const_cast<void*>(state)), div,
+                        out, static_cast<uint32_t*>(nullptr));
 }
 
 int ptg_last_counters(ptg_context* ctx, uint64_t out[8])

@@ -29,6 +29,24 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _span(cfg, rect=None, samples=None):
+    """(x0, y0, w, h, j0, j1): `rect` and the sample range `samples` with
+    their defaults, the whole image and every sample of `cfg`."""
+    x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
+    j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
+    return x0, y0, w, h, j0, j1
+
+
+def _planes(device, h, w, *want):
+    """Empty planes of an [h, w] image on `device` (a torch.device or a GPU
+    ordinal), one per entry of `want` and None where the entry is false: the
+    first is bgra, uint8 [h, w, 4], every other one float32 [h, w, 4]."""
+    import torch
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", device)
+    return tuple(torch.empty((h, w, 4), dtype=torch.float32 if k else torch.uint8, device=dev) if on else None
+                 for k, on in enumerate(want))
+
+
 class GpuRenderer:
     def __init__(self, device: int = 0, stream=None):
         import torch  # noqa: F401  (device memory + streams)
@@ -86,14 +104,10 @@ class GpuRenderer:
         image) and sample range `samples` = (begin, end) (default: all).
         Returns (bgra uint8 [h, w, 4], accum float32 [h, w, 4] or None) as
         torch tensors on this GPU.  Asynchronous on the context stream."""
-        import torch
-        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
-        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
-        dev = torch.device("cuda", self.device)
-        if out_bgra is None:
-            out_bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
-        if out_accum is None and want_accum:
-            out_accum = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        x0, y0, w, h, j0, j1 = _span(cfg, rect, samples)
+        bgra, accum = _planes(self.device, h, w, out_bgra is None, want_accum and out_accum is None)
+        out_bgra = out_bgra if out_bgra is not None else bgra
+        out_accum = out_accum if out_accum is not None else accum
         N.check(N.lib().ptg_render(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(out_accum), _ptr(out_bgra)),
                 "ptg_render")
         return out_bgra, out_accum
@@ -139,10 +153,7 @@ class GpuRenderer:
         import torch
         assert packs.dtype == torch.uint8 and packs.is_contiguous()
         assert packs.numel() == world * N.lib().ptg_tile_pack_bytes(tile_w, tile_h, pack_tiles)
-        h, w = cfg.height, cfg.width
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=packs.device)
-        accum, moments, albedo, normal_depth = (torch.empty((h, w, 4), dtype=torch.float32, device=packs.device)
-                                                for _ in range(4))
+        bgra, accum, moments, albedo, normal_depth = _planes(packs.device, cfg.height, cfg.width, *[True] * 5)
         N.check(N.lib().ptg_assemble_tile_packs(self._ctx, C.byref(cfg), tile_w, tile_h, world, pack_tiles, _ptr(packs),
                                                 _ptr(accum), _ptr(bgra), _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
                 "ptg_assemble_tile_packs")
@@ -192,12 +203,8 @@ class GpuRenderer:
         """First-hit feature buffers over `rect` and sample range `samples`
         (defaults as render()): (albedo+coverage, normal+depth), two float32
         [h, w, 4] torch tensors on this GPU.  Asynchronous."""
-        import torch
-        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
-        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
-        dev = torch.device("cuda", self.device)
-        albedo = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-        normal_depth = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        x0, y0, w, h, j0, j1 = _span(cfg, rect, samples)
+        _, albedo, normal_depth = _planes(self.device, h, w, False, True, True)
         N.check(N.lib().ptg_render_features(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(albedo),
                                             _ptr(normal_depth)), "ptg_render_features")
         return albedo, normal_depth
@@ -230,13 +237,8 @@ class GpuRenderer:
         albedo+coverage, normal+depth), each with the bits the separate calls
         give.  On the wavefront pipeline the features come from the render's
         own primary rays, so no second walk is made.  Asynchronous."""
-        import torch
-        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
-        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
-        dev = torch.device("cuda", self.device)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
-        accum, albedo, normal_depth = (torch.empty((h, w, 4), dtype=torch.float32, device=dev) for _ in range(3))
-        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if want_moments else None
+        x0, y0, w, h, j0, j1 = _span(cfg, rect, samples)
+        bgra, accum, moments, albedo, normal_depth = _planes(self.device, h, w, True, True, want_moments, True, True)
         N.check(N.lib().ptg_render_with_features(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(accum), _ptr(bgra),
                                                  _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
                 "ptg_render_with_features")
@@ -262,13 +264,8 @@ class GpuRenderer:
         (mean, second moment, variance of the mean, finite samples)).  The
         moments are normalised by the finite samples of the range rendered.
         Asynchronous."""
-        import torch
-        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
-        j0, j1 = samples if samples is not None else (0, cfg.samples_per_pixel)
-        dev = torch.device("cuda", self.device)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
-        accum = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if want_accum else None
-        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        x0, y0, w, h, j0, j1 = _span(cfg, rect, samples)
+        bgra, accum, moments = _planes(self.device, h, w, True, want_accum, True)
         N.check(N.lib().ptg_render_moments(self._ctx, C.byref(cfg), x0, y0, w, h, j0, j1, _ptr(accum), _ptr(bgra),
                                            _ptr(moments)), "ptg_render_moments")
         return bgra, accum, moments
@@ -303,12 +300,9 @@ class GpuRenderer:
         import torch
         from .adaptive import AdaptiveParams
         p = params if params is not None else AdaptiveParams.default()
-        x0, y0, w, h = rect if rect is not None else (0, 0, cfg.width, cfg.height)
-        dev = torch.device("cuda", self.device)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
-        accum = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-        moments = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-        samples = torch.empty((h, w), dtype=torch.int32, device=dev)
+        x0, y0, w, h, _, _ = _span(cfg, rect)
+        bgra, accum, moments = _planes(self.device, h, w, True, True, True)
+        samples = torch.empty((h, w), dtype=torch.int32, device=bgra.device)
         N.check(N.lib().ptg_render_adaptive(self._ctx, C.byref(cfg), x0, y0, w, h, C.byref(p), _ptr(accum), _ptr(bgra),
                                             _ptr(moments), _ptr(samples)), "ptg_render_adaptive")
         return bgra, accum, moments, samples
@@ -602,14 +596,9 @@ class Accumulator:
         bits of the one-shot render of the same sample range), by_samples=True
         by the samples taken (a preview at the final brightness).  The state
         is not changed.  Asynchronous."""
-        import torch
         _, _, w, h = self.rect
-        dev = self.state.device
-        new = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-        bgra = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
-        accum = new()
-        moments = new() if self.moments else None
-        albedo, normal_depth = (new(), new()) if self.features else (None, None)
+        bgra, accum, moments, albedo, normal_depth = _planes(self.state.device, h, w, True, True, self.moments,
+                                                             self.features, self.features)
         N.check(N.lib().ptg_accum_resolve(self.renderer._ctx, C.byref(self.header), _ptr(self.state), 1 if by_samples else 0,
                                           _ptr(accum), _ptr(bgra), _ptr(moments), _ptr(albedo), _ptr(normal_depth)),
                 "ptg_accum_resolve")
