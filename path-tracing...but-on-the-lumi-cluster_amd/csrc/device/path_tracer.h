@@ -168,9 +168,7 @@ struct WalkCold {              // one lane's LDS slot: two b128 accesses
 // route at run time (HIP's float4/uint2 classes cannot be assigned through
 // an address-space pointer)
 typedef float lds_f4v __attribute__((ext_vector_type(4)));
-typedef uint32_t lds_u2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) lds_f4v lds_cold_t;   // [0] = WalkCold::o, [1] = WalkCold::d
-typedef __attribute__((address_space(3))) lds_u2v lds_uint2_t;
 
 // World ray in LDS (read at BLAS entry and exit), best hit in registers.
 struct LdsCold {
@@ -249,10 +247,12 @@ struct PrivStack {
 };
 
 // LdsStack: the wavefront walks' stack.  The newest entries of a lane live
-// in LDS, in a window of kCap slots (one 8-byte column per lane: slot k of a
-// wave's 64 lanes is one conflict-free 512 B row), addressed through a
-// pointer to the next free slot, so a push is one ds_write at that pointer
-// and a pointer bump.  When a block step could overflow the window, its
+// in LDS, in a window of kCap slots.  Slot k of a wave's 64 lanes is one
+// 512 B row of two conflict-free 4-byte planes, the 64 words and then the 64
+// nears, addressed through a pointer to the lane's next free slot: a push is
+// one two-address ds_write (both source registers as they are, no register
+// pair to build) at that pointer and a pointer bump, a pop the matching
+// two-address read.  When a block step could overflow the window, its
 // oldest half goes to the lane's area in HBM and the rest moves down (rare);
 // those entries come back one by one when the stack unwinds to them.  A
 // 16-entry window holds the whole stack for all but ~0.03 entries per query
@@ -262,15 +262,17 @@ struct PrivStack {
 #endif
 struct LdsStack {
     static constexpr uint32_t kCap = PTG_STACK_ENTRIES;
-    lds_uint2_t* s;            // the lane's window column: slot k at s[64 * k]
-    lds_uint2_t* t;            // next free slot: s + 64 * (sp - lo)
+    typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+    static constexpr uint32_t kRow = 128;   // 4-byte words per slot row: 64 words, then 64 nears
+    lds_u32_t* s;              // the lane's window column: slot k's word at s[kRow * k], its near at s[kRow * k + 64]
+    lds_u32_t* t;              // next free slot: s + kRow * (sp - lo)
     uint2* g;                  // the lane's spill area (HBM)
     uint32_t sp, lo;           // entries; entries below lo are in HBM
     static constexpr uint32_t kLaneBytes = 8u * kCap;   // LDS per lane
-    // windows: one 64-lane x kCap table per wave from `lds` on; `spill`: the lane's area
+    // windows: one kCap-row table per wave from `lds` on; `spill`: the lane's area
     PTG_D void bind(void* lds, uint32_t wave, uint32_t lane, uint2* spill)
     {
-        s = (lds_uint2_t*)(reinterpret_cast<uint2*>(lds) + wave * (64u * kCap) + lane);   // C cast: generic -> LDS
+        s = (lds_u32_t*)(reinterpret_cast<uint32_t*>(lds) + wave * (kRow * kCap) + lane);   // C cast: generic -> LDS
         g = spill;
     }
     PTG_D void reset()
@@ -284,22 +286,26 @@ struct LdsStack {
     {
         if(sp - lo + n <= kCap) return;
         const uint32_t in = sp - lo, h = in > 1 ? in / 2 : in;
-        for(uint32_t i = 0; i < h; ++i)
+#pragma nounroll
+        for(uint32_t i = 0; i < h; ++i) g[lo + i] = make_uint2(s[kRow * i], s[kRow * i + 64u]);
+#pragma nounroll
+        for(uint32_t i = h; i < in; ++i)
         {
-            const lds_u2v v = s[64u * i];
-            g[lo + i] = make_uint2(v.x, v.y);
+            const uint32_t w = s[kRow * i], n2 = s[kRow * i + 64u];
+            s[kRow * (i - h)] = w;
+            s[kRow * (i - h) + 64u] = n2;
         }
-        for(uint32_t i = h; i < in; ++i) s[64u * (i - h)] = s[64u * i];
         lo += h;
-        t = s + 64u * (sp - lo);
+        t = s + kRow * (sp - lo);
     }
     // write e at the top; keep it (push) iff `keep`
     PTG_D void put(uint2 e, bool keep)
     {
-        *t = lds_u2v{e.x, e.y};
+        t[0] = e.x;
+        t[64] = e.y;
         if(keep)
         {
-            t += 64;
+            t += kRow;
             ++sp;
         }
     }
@@ -311,9 +317,8 @@ struct LdsStack {
             lo = sp;
             return g[sp];
         }
-        t -= 64;
-        const lds_u2v v = *t;
-        return make_uint2(v.x, v.y);
+        t -= kRow;
+        return make_uint2(t[0], t[64]);
     }
     // whether n more entries fit the lane's spill area of `stride` entries (PTG_DEBUG)
     PTG_D bool fits(uint32_t n, uint32_t stride) const { return sp + n <= stride; }
@@ -468,8 +473,16 @@ struct BlockWalker {
     float tmin, tmax;
     f3 org, inv;               // active level: ray origin / 1/dir in that level's space
     f3 winv;                   // the world ray's 1/dir (the TLAS level's inv)
-    bool fin;                  // active level: every component of inv finite (box_near_far applies)
-    uint32_t oct;              // active level: direction octant (the links' order index, ray_query.hh:139-140)
+    // active level: the direction octant (the links' order index,
+    // ray_query.hh:139-140) as the byte offset of its copy in a block (bits
+    // 7..29), and whether every component of inv is finite (bit 31:
+    // box_near_far applies); the same two of the world ray, which a BLAS exit
+    // restores, in bits 0..2 (the octant itself) and bit 30
+    uint32_t oct;
+    static constexpr uint32_t kOctFin = 0x80000000u, kOctWorldFin = 0x40000000u, kOctWorld = 7u;
+    static constexpr uint32_t kOctOffset = ~(kOctFin | kOctWorldFin | kOctWorld);
+    static_assert(sizeof(BlockCopy) % 8 == 0 && 7u * sizeof(BlockCopy) < kOctWorldFin, "oct's fields overlap");
+    PTG_D bool fin_now() const { return int32_t(oct) < 0; }
     f3 S;                      // BLAS: shear constants of ray_triangle_intersection_preprocess
     int axis;                  // BLAS: dominant axis, -1 while in the TLAS (blas_axis)
     uint32_t tri_base, inst, bsp;
@@ -489,8 +502,8 @@ struct BlockWalker {
         org = ro;
         inv = iw;
         winv = iw;
-        fin = finite3(iw);
-        oct = octant(rd);
+        const uint32_t o = octant(rd);
+        oct = o | o * uint32_t(sizeof(BlockCopy)) | (finite3(iw) ? kOctFin | kOctWorldFin : 0u);
         S = V3(0, 0, 0);
         axis = -1;
         tri_base = 0;
@@ -607,7 +620,7 @@ struct BlockWalker {
         tri_base = __float_as_uint(b.w);
         inst = leaf;
         bsp = st.size();
-        oct = octant(bd);
+        const uint32_t world = oct & (kOctWorldFin | kOctWorld);
         bool ok = true;   // one fallback branch for the four reciprocals of the entry
         inv = V3(rcp_nr(bd.x, ok), rcp_nr(bd.y, ok), rcp_nr(bd.z, ok));
         // ray_triangle_intersection_preprocess (math.hh:340-356)
@@ -623,7 +636,7 @@ struct BlockWalker {
             k = 1.0f / rd.z;
         }
         S = V3(rd.x * k, rd.y * k, 1.0f * k);
-        fin = finite3(inv);
+        oct = world | octant(bd) * uint32_t(sizeof(BlockCopy)) | (finite3(inv) ? kOctFin : 0u);
     }
 
     // ray_query_test_triangle + ray_triangle_intersection (ray_query.hh:225-246,
@@ -686,8 +699,8 @@ struct BlockWalker {
             axis = -1;
             org = cold.world_o();
             inv = winv;
-            fin = finite3(winv);
-            oct = octant(cold.world_d());
+            const uint32_t world = oct & (kOctWorldFin | kOctWorld);
+            oct = world | (world & kOctWorld) * uint32_t(sizeof(BlockCopy)) | ((world & kOctWorldFin) << 1);
             if(st.size() == 0) return 1;   // (ANY: resume_tlas may go on)
         }
         const uint2 e = st.pop();
@@ -710,7 +723,7 @@ struct BlockWalker {
     {   // a 32-bit byte offset from the buffer's base (the upload keeps the
         // block buffer below 4 GB), so the loads take the scalar-base +
         // vector-offset form instead of 64-bit address arithmetic per lane
-        const uint32_t off = (cur * kBlockCopies + oct) * uint32_t(sizeof(BlockCopy));
+        const uint32_t off = cur * (kBlockCopies * uint32_t(sizeof(BlockCopy))) + (oct & kOctOffset);
         return reinterpret_cast<const v4f*>(reinterpret_cast<const uint8_t*>(sc.blocks) + off);
     }
     // float k of the packed far planes (rows kBlockWidth..): entry j's at 3j..3j+2
@@ -721,9 +734,13 @@ struct BlockWalker {
         return c == 0 ? r.x : c == 1 ? r.y : c == 2 ? r.z : r.w;
     }
 
-    // Node phase, second half: the block step on its rows.
+    // the float after tmin (node_block's clamp of the entry distance)
+    PTG_D float tmin_next() const { return __uint_as_float(__float_as_uint(tmin) + 1u); }
+
+    // Node phase, second half: the block step on its rows.  tmin_p: tmin_next(),
+    // which a caller whose tmin is the same for every walk computes once.
     template<bool COUNT>
-    PTG_D int node_block(const DevScene& sc, Counters& cnt, const v4f (&q)[kBlockRows])
+    PTG_D int node_block(const DevScene& sc, Counters& cnt, const v4f (&q)[kBlockRows], float tmin_p)
     {
         // rows 0..W-1: entry j's near planes and word; then the far planes, packed
         constexpr uint32_t W = kBlockWidth;
@@ -742,9 +759,8 @@ struct BlockWalker {
         // branch, so the two branches merge an integer, not four lane masks
         // (a merge of lane masks costs exec-masked scalar and/or per mask)
         uint32_t hits = 0;
-        if(__all(fin))
+        if(__all(fin_now()))
         {   // every lane's reciprocal finite (the rule): no per-axis min/max
-            const float tmin_p = __uint_as_float(__float_as_uint(tmin) + 1u);
             const float tmax_m = __uint_as_float(__float_as_uint(tmax) - 1u);
 #pragma unroll
             for(uint32_t j = 0; j < W; ++j) hits |= box_near_far(l[j], h[j], tmin_p, tmax_m, nr[j]) ? (1u << j) : 0u;
@@ -759,7 +775,6 @@ struct BlockWalker {
             // confirmed t > tmin); at tmax == tmin_p no triangle can be
             // accepted any more.  A pushed near is then a positive float
             // (LdsSlotStack tells its slots from leaf words by the top bit).
-            const float tmin_p = __uint_as_float(__float_as_uint(tmin) + 1u);
 #pragma unroll
             for(uint32_t j = 0; j < W; ++j)
             {
@@ -815,7 +830,9 @@ struct BlockWalker {
     // block, one block step.  Returns 1 when the walk has ended, else 0 (the
     // walk may then stand at a leaf, which leaf_step() takes).
     template<bool COUNT>
-    PTG_D int node_step(const DevScene& sc, Counters& cnt)
+    PTG_D int node_step(const DevScene& sc, Counters& cnt) { return node_step<COUNT>(sc, cnt, tmin_next()); }
+    template<bool COUNT>
+    PTG_D int node_step(const DevScene& sc, Counters& cnt, float tmin_p)
     {
         if(const int r = node_pop(); r >= 0) return r;
         PTG_CHECK(sc, cur < sc.block_count, kDebugNode);
@@ -823,7 +840,7 @@ struct BlockWalker {
         v4f q[kBlockRows];
 #pragma unroll
         for(uint32_t k = 0; k < kBlockRows; ++k) q[k] = p[k];
-        return node_block<COUNT>(sc, cnt, q);
+        return node_block<COUNT>(sc, cnt, q, tmin_p);
     }
 
     // Leaf phase, first half: the parked triangle, else the BLAS entry or

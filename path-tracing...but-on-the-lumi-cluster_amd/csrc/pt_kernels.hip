@@ -315,7 +315,10 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
     // XCD's bands (balanced) and the waves in flight cover a narrow window.
     const uint32_t xcd = blockIdx.x % nxcd;
     const uint32_t waves = ((gridDim.x / nxcd) * blockDim.x) >> 6;
-    const uint32_t wave = ((blockIdx.x / nxcd) * blockDim.x + threadIdx.x) >> 6;
+    // (the same for a wave's 64 lanes: in a scalar register, and with it the
+    // wave's range of the queue and its cursor, so the refill test at the top
+    // of every iteration is a scalar compare)
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(((blockIdx.x / nxcd) * blockDim.x + threadIdx.x) >> 6);
     const uint32_t groups = (n + 63u) >> 6;
     const uint32_t band = max(1u, (groups + kBands - 1u) / kBands);
     const uint32_t local = (kBands / nxcd) * band;    // this XCD's group slots (some past the end)
@@ -335,6 +338,7 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
     uint32_t cursor = 0;
     const float tmin = (ANY || round > 0) ? MIN_RAY_DIST : 0.0f;
     const float tmax = ANY ? MAX_RAY_DIST : 1e9f;
+    const float tmin_p = __uint_as_float(__float_as_uint(tmin) + 1u);   // BlockWalker::tmin_next() of every walk here
     Counters cnt;
     // LDS: every lane's world ray, then the stack windows, one 64-lane x kCap
     // entry table per wave (ptg_context_create sizes the block's LDS)
@@ -440,17 +444,21 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
         // lanes that are.  The leaf code (triangle test, BLAS entry) then runs
         // once per iteration with many lanes, not once per block step with few.
         int r = 0;
+        // A walk that ends in any phase of this iteration only leaves
+        // `active`; the one finish site after the leaf phase writes its
+        // result (q and the walk's best hit stay as they are until the next
+        // refill, at the top of the next iteration).
+        const bool was_active = active;
 #pragma unroll
         for(int u = 0; u < kWalkUnroll; ++u)
         {
             if(COUNT) cnt.step_loads = 0;
-            if(active && !w.at_leaf()) r = w.template node_step<COUNT>(sc, cnt);   // (a lane with a parked triangle walks on)
+            if(active && !w.at_leaf()) r = w.template node_step<COUNT>(sc, cnt, tmin_p);   // (a lane with a parked triangle walks on)
             if(COUNT) tally(WS_NODE_WAVES, (cnt.step_loads & 1u) != 0);
             if(active && r != 0)
             {   // ANY: after a candidate's instance, the TLAS (BlockWalker::resume_tlas)
                 if(!(ANY && w.resume_tlas()))
                 {
-                    finish(r);
                     active = false;
                 }
                 r = 0;
@@ -472,8 +480,9 @@ __global__ __launch_bounds__(kBlock) PTG_WALK_ATTR void k_wf_walk(DevScene sc, P
         {
             r = w.template leaf_step<ANY, COUNT>(sc, cnt);
             occluded = ANY && r == 2;
-            if(r != 0) { finish(r); active = false; }
+            if(r != 0) active = false;
         }
+        if(was_active && !active) finish(occluded ? 2 : 1);
         if(ANY)
         {   // the wave's candidate becomes an occluder one of its lanes just found
             const unsigned long long om = __ballot(occluded);
